@@ -10,6 +10,11 @@ synchronous like the reference's compute() (src/CLCaster.cpp:224-228, clFinish :
 (SVO, ray table, atlas) are resident in HBM before the timed region; the frame is the production frame (the image and
 nothing else, like the reference: setting hit_records = 0).  Prints ONE JSON line on rank 0.
 
+A plain run only sets up, warms up, times the --steps frames and prints the line (metric, value, unit, ms_per_step, config).
+--full adds everything else the benchmark measures or checks: value_no_prewarm, the roofline (one more frame without the empty
+boxes), the survey-camera pose, the other BASELINE configs, the hit-record / two-frames / mode-B legs and the CPU baselines.
+--dump-outputs DIR writes the frame the last timed step rendered to DIR/image.npy (float32, H x W x 4: what read_image returns).
+
 N = 1: BASELINE.json configs[2] -- 4096^3 shell-terrain SVO (seed 1), 1920x1080, primary rays +
 one shadow ray per hit + Blinn-Phong + atlas, the reference's own ray table.
 N > 1, --scaling weak (default): the frame grows to 1920 x (1080*N) rows over the SAME field of view (vertical
@@ -330,6 +335,29 @@ def shared_scene(depth, rank, world, tag, dist_on=False, thickness=2):
     return sc, path
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(c, out_dir, rank, world, full_h):
+    """--dump-outputs: what the last timed step computed, as a caller of compute() receives it -- read_image's float32 RGBA
+    frame, rows x width x 4 -- so that two builds can be compared output for output (the scene, camera and lights are seeded).
+    One GPU writes DIR/image.npy; under N > 1 every rank writes its own rows to DIR/image_rank<r>.npy.  A frame larger than
+    its share of 64 MB keeps a fixed, seeded sample of its rows; the row indices then go to image[_rank<r>]_rows.npy (float64)."""
+    from voxel_raycaster_amd import tiling
+    w, _ = c.viewport_size
+    img = c.read_image(np.zeros((full_h, w, 4), dtype=np.float32))       # a row-sliced handle fills only its own rows
+    rows = np.arange(full_h) if world == 1 else np.asarray(tiling.rows_of_rank(full_h, rank, world, 8))
+    keep = (DUMP_LIMIT_BYTES // world) // (w * 16 + 8)
+    sampled = rows.size > keep
+    if sampled:
+        rows = np.sort(np.random.default_rng(20261016).choice(rows, size=keep, replace=False))
+    name = "image" if world == 1 else f"image_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), img[rows])
+    if sampled or world > 1:
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -353,7 +381,14 @@ def main():
                          "library must not be inherited by child processes of a GPU-initialised program)")
     ap.add_argument("--pmc-traffic", type=str, default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="JSON file with the rocprofv3 PMC measurement of HBM bytes per launch (see DESIGN.md 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the supplementary legs (value_no_prewarm, roofline, survey_camera, other_configs, hit records, two frames "
+                         "in flight, mode B, CPU baselines); a plain run times the headline frame only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/image.npy (float32; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -427,17 +462,18 @@ def main():
     t_first = time.perf_counter()
     assert c.compute(), c.last_error()
     first_compute_ms = (time.perf_counter() - t_first) * 1e3
-    canonical_ctr = canonical_counters(c)
-    assert c.compute(), c.last_error()
-    ctr0 = c.counters()
-    torch.cuda.synchronize()
-    tc = time.perf_counter()
-    for _ in range(args.steps):
-        if not c.compute():
-            raise SystemExit("compute failed: " + c.last_error())
-    torch.cuda.synchronize()
-    cold_dt = time.perf_counter() - tc
-    value_no_prewarm = (ctr0["primary_rays"] + ctr0["shadow_rays"]) * args.steps / cold_dt / 1e6      # this rank's rows
+    if args.full:
+        canonical_ctr = canonical_counters(c)
+        assert c.compute(), c.last_error()
+        ctr0 = c.counters()
+        torch.cuda.synchronize()
+        tc = time.perf_counter()
+        for _ in range(args.steps):
+            if not c.compute():
+                raise SystemExit("compute failed: " + c.last_error())
+        torch.cuda.synchronize()
+        cold_dt = time.perf_counter() - tc
+        value_no_prewarm = (ctr0["primary_rays"] + ctr0["shadow_rays"]) * args.steps / cold_dt / 1e6      # this rank's rows
 
     # set-up, not measurement: a fresh process finds the GPU at its idle clocks, and a 3 ms kernel needs a few dozen
     # launches before DVFS settles (measured: the first timed block of a run is 2-3 % slower than the second)
@@ -464,55 +500,12 @@ def main():
     dt = time.perf_counter() - t0
 
     n_launch, kernel_ms = c.timing()
+    if args.dump_outputs:
+        dump_outputs(c, args.dump_outputs, rank, world, full_h)
     total_rays, max_dt = reduce_over_ranks(rays_per_step, dt)
     value = total_rays * args.steps / max_dt / 1e6
 
     if rank == 0:
-        from voxel_raycaster_amd import tiling
-        local_pixels = W * len(tiling.rows_of_rank(full_h, rank, world, 8))
-        written = local_pixels - ctr["unwritten_pixels"]
-        bytes_per_launch = algorithmic_bytes(canonical_ctr, local_pixels, written)
-        avg_kernel_s = kernel_ms / max(n_launch, 1) / 1e3
-        achieved = bytes_per_launch / avg_kernel_s / 1e9
-        # HBM bytes and VALU instructions per launch come from rocprofv3 PMC passes (tools/gpu_profile.sh: counters cannot be
-        # read inside this process).  The committed measurement is stamped with the hash of the kernel sources it was
-        # taken on; a different kernel => null, never a stale number.
-        traffic, issue, pmc_note, traffic_split = None, None, "no PMC measurement for this workload", None
-        headline = (args.depth, W, H, args.lights, args.shadow_rays, args.thickness) == (12, 1920, 1080, 1, 1, 2)
-        if world == 1 and headline and args.pmc_traffic and os.path.exists(args.pmc_traffic):
-            pmc = json.load(open(args.pmc_traffic))
-            if pmc.get("kernel_source_hash") == kernel_source_hash():
-                traffic = pmc.get("hbm_bytes_per_launch")
-                pmc_note = pmc.get("source")
-                # what the one `traffic` number is made of: reads (FETCH_SIZE, doubled per the guide's gfx950 correction), writes
-                # (WRITE_SIZE), and the part of the writes that is the frame itself -- the rest of the writes is scratch and the
-                # jump tables' rows written through
-                if pmc.get("fetch_size_kib_raw") is not None:
-                    traffic_split = {"fetch_bytes": int(2 * pmc["fetch_size_kib_raw"] * 1024), "write_bytes": int(pmc["write_size_kib_raw"] * 1024),
-                                     "frame_bytes": int(16 * written),
-                                     "write_over_frame": round(pmc["write_size_kib_raw"] * 1024 / max(16 * written, 1), 2),
-                                     "algorithmic_descriptor_bytes": int(8 * canonical_ctr["descriptor_reads"])}
-                valu = pmc.get("valu_insts_per_launch")
-                if valu:
-                    # the float recurrence of ray_caster_kernel.cl:558-559 (min, three masks, three fused updates = 10 wave64
-                    # instructions per 64 lane steps) is what any kernel that steps voxel by voxel must issue at least; the
-                    # closed-form jumps (exact_jump.hpp) are how this one gets below 12 per step on average
-                    floor = ctr["steps"] / 64.0 * 10.0
-                    rate = valu / avg_kernel_s / 1e9
-                    issue = {"valu_insts_per_launch": int(valu), "per_voxel_stepping_floor_insts": int(floor),
-                             "valu_over_stepping_floor": round(valu / floor, 4),
-                             "achieved_ginst_s": round(rate, 1), "peak_ginst_s": VALU_PEAK_GINST_S,
-                             "frac": round(rate / VALU_PEAK_GINST_S, 4),
-                             "note": "frac counts instructions; frac_time_weighted weighs every instruction class with its measured issue interval"}
-                    tw = pmc.get("valu_time_weighted")
-                    if tw:
-                        # share of the launch's SIMD cycles in which a VALU instruction is being issued: per-class counts
-                        # (SQ_INSTS_VALU_<class>) x the issue interval tools/ubench/valu_issue.hip measures for the class
-                        issue.update({"frac_time_weighted": tw["frac_time_weighted"], "frac_time_weighted_range": tw["frac_time_weighted_range"],
-                                      "issue_cycles_per_launch": int(tw["issue_cycles_mid"]), "simd_cycles_per_launch": int(tw["simd_cycles_per_launch"]),
-                                      "classes": tw["classes"], "time_weighted_source": tw["source"]})
-            else:
-                pmc_note = "profiles/traffic_latest.json was measured on other kernel sources: re-run tools/gpu_profile.sh + tools/update_profiles.py"
         n_desc = int(sc["octree"].descriptor_buffer.size) if sc.get("octree") is not None else int(sc.get("n_desc", 0))
         rehearsal_note = ("ranks share GPU 0 over gloo (VRC_BENCH_REHEARSAL): a rehearsal of the N > 1 code path, not a scaling measurement"
                           if rehearsal else None)
@@ -521,7 +514,6 @@ def main():
             "value": round(value, 3), "unit": "Mrays/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(max_dt / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": "weak" if (world == 1 or not strong) else "strong",
-            "value_no_prewarm": round(value_no_prewarm, 3) if world == 1 else None,
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": workload_name(args, sc, W, H, world, strong),
                        "descriptors": n_desc,
@@ -536,39 +528,94 @@ def main():
                                    "the empty boxes the tree's device-side pass found around them (empty_boxes.hip, setting empty_boxes): fewer node "
                                    "events, the same steps",
                        "prewarm_frames": PREWARM_FRAMES,
-                       "frame": "production frame: image only, like the reference (hit_records = 0); with_hit_records is the same frame plus the parity records",
+                       "frame": "production frame: image only, like the reference (hit_records = 0); with_hit_records (--full) is the same frame plus the parity records",
                        "multi_gpu": ("no N > 1 hardware measurement is recorded in this repository (SCALE_r01..r03 were skipped: no 8-GPU node); "
                                      "an N > 1 line is only a measurement when the driver launched it on N distinct GPUs"
                                      + ("; THIS line: " + rehearsal_note if rehearsal_note else ""))},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_split": traffic_split,
-                         "algorithmic_bytes_per_launch": int(bytes_per_launch),
-                         "kernel_ms_avg": round(avg_kernel_s * 1e3, 4), "kernel": "raycast_svo_kernel",
-                         "binding_roof": "valu_issue",
-                         "note": "exact-parity traversal is bound by VALU issue and by the latency of its dependent chains (DESIGN.md 4), not by "
-                                 "HBM: frac is kept on HBM as BASELINE defines it, valu_issue says what the kernel issues",
-                         "descriptor_reads": canonical_ctr["descriptor_reads"],
-                         "descriptor_reads_note": "SURVEY 8d's canonical count (one untimed frame with empty_boxes = 0); the timed frames use the "
-                                                  "tree's empty boxes and read " + str(ctr["descriptor_reads"]) + " descriptors + table cells",
-                         "steps": ctr["steps"], "valu_issue": issue, "kernel_instance": kernel_instance(c, sc, args.lights),
-                         "tree_state": tree_state(c, first_compute_ms, max_dt / args.steps * 1e3),
-                         "pmc_source": pmc_note, "kernel_source_hash": kernel_source_hash()},
         }
-        if world == 1 and not sc.get("device_built") and not args.no_survey_camera:
-            out["survey_camera"] = survey_camera_leg(sc, c, args)
-        if world == 1 and headline and not args.no_other_configs and not args.no_survey_camera:
-            try:
-                out["other_configs"] = other_configs(sc, c, local_rank, args)
-            except Exception as e:                 # a supplementary leg must never take the headline line down
-                out["other_configs"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline and not sc.get("device_built"):
-            out.update(supplementary(sc, c, W, H, local_rank, args, rays_per_step))
+        if args.full:
+            out["value_no_prewarm"] = round(value_no_prewarm, 3) if world == 1 else None
+            out["roofline"] = roofline_report(c, sc, args, ctr, canonical_ctr, n_launch, kernel_ms, W, H, full_h, rank, world, max_dt,
+                                              first_compute_ms)
+            headline = (args.depth, W, H, args.lights, args.shadow_rays, args.thickness) == (12, 1920, 1080, 1, 1, 2)
+            if world == 1 and not sc.get("device_built") and not args.no_survey_camera:
+                out["survey_camera"] = survey_camera_leg(sc, c, args)
+            if world == 1 and headline and not args.no_other_configs and not args.no_survey_camera:
+                try:
+                    out["other_configs"] = other_configs(sc, c, local_rank, args)
+                except Exception as e:                 # a supplementary leg must never take the headline line down
+                    out["other_configs"] = {"error": str(e)}
+            if world == 1 and not args.no_cpu_baseline and not sc.get("device_built"):
+                out.update(supplementary(sc, c, W, H, local_rank, args, rays_per_step))
         if dist_on and world == 1:
             out["config"]["distributed_path"] = f"forced on a world of one ({dist.get_backend()}): barrier, broadcast_object_list, all_reduce executed"
         print(json.dumps(out), flush=True)
     if dist_on:
         barrier(local_rank)
         dist.destroy_process_group()
+
+
+def roofline_report(c, sc, args, ctr, canonical_ctr, n_launch, kernel_ms, W, H, full_h, rank, world, max_dt, first_compute_ms):
+    """--full: the timed frames against the HBM roof (SURVEY 8d's algorithmic bytes, priced with the canonical read count of
+    the untimed frame without the empty boxes), the PMC figures measured on these kernel sources, and what the tree costs."""
+    from voxel_raycaster_amd import tiling
+    local_pixels = W * len(tiling.rows_of_rank(full_h, rank, world, 8))
+    written = local_pixels - ctr["unwritten_pixels"]
+    bytes_per_launch = algorithmic_bytes(canonical_ctr, local_pixels, written)
+    avg_kernel_s = kernel_ms / max(n_launch, 1) / 1e3
+    achieved = bytes_per_launch / avg_kernel_s / 1e9
+    # HBM bytes and VALU instructions per launch come from rocprofv3 PMC passes (tools/gpu_profile.sh: counters cannot be
+    # read inside this process).  The committed measurement is stamped with the hash of the kernel sources it was
+    # taken on; a different kernel => null, never a stale number.
+    traffic, issue, pmc_note, traffic_split = None, None, "no PMC measurement for this workload", None
+    headline = (args.depth, W, H, args.lights, args.shadow_rays, args.thickness) == (12, 1920, 1080, 1, 1, 2)
+    if world == 1 and headline and args.pmc_traffic and os.path.exists(args.pmc_traffic):
+        pmc = json.load(open(args.pmc_traffic))
+        if pmc.get("kernel_source_hash") == kernel_source_hash():
+            traffic = pmc.get("hbm_bytes_per_launch")
+            pmc_note = pmc.get("source")
+            # what the one `traffic` number is made of: reads (FETCH_SIZE, doubled per the guide's gfx950 correction), writes
+            # (WRITE_SIZE), and the part of the writes that is the frame itself -- the rest of the writes is scratch and the
+            # jump tables' rows written through
+            if pmc.get("fetch_size_kib_raw") is not None:
+                traffic_split = {"fetch_bytes": int(2 * pmc["fetch_size_kib_raw"] * 1024), "write_bytes": int(pmc["write_size_kib_raw"] * 1024),
+                                 "frame_bytes": int(16 * written),
+                                 "write_over_frame": round(pmc["write_size_kib_raw"] * 1024 / max(16 * written, 1), 2),
+                                 "algorithmic_descriptor_bytes": int(8 * canonical_ctr["descriptor_reads"])}
+            valu = pmc.get("valu_insts_per_launch")
+            if valu:
+                # the float recurrence of ray_caster_kernel.cl:558-559 (min, three masks, three fused updates = 10 wave64
+                # instructions per 64 lane steps) is what any kernel that steps voxel by voxel must issue at least; the
+                # closed-form jumps (exact_jump.hpp) are how this one gets below 12 per step on average
+                floor = ctr["steps"] / 64.0 * 10.0
+                rate = valu / avg_kernel_s / 1e9
+                issue = {"valu_insts_per_launch": int(valu), "per_voxel_stepping_floor_insts": int(floor),
+                         "valu_over_stepping_floor": round(valu / floor, 4),
+                         "achieved_ginst_s": round(rate, 1), "peak_ginst_s": VALU_PEAK_GINST_S,
+                         "frac": round(rate / VALU_PEAK_GINST_S, 4),
+                         "note": "frac counts instructions; frac_time_weighted weighs every instruction class with its measured issue interval"}
+                tw = pmc.get("valu_time_weighted")
+                if tw:
+                    # share of the launch's SIMD cycles in which a VALU instruction is being issued: per-class counts
+                    # (SQ_INSTS_VALU_<class>) x the issue interval tools/ubench/valu_issue.hip measures for the class
+                    issue.update({"frac_time_weighted": tw["frac_time_weighted"], "frac_time_weighted_range": tw["frac_time_weighted_range"],
+                                  "issue_cycles_per_launch": int(tw["issue_cycles_mid"]), "simd_cycles_per_launch": int(tw["simd_cycles_per_launch"]),
+                                  "classes": tw["classes"], "time_weighted_source": tw["source"]})
+        else:
+            pmc_note = "profiles/traffic_latest.json was measured on other kernel sources: re-run tools/gpu_profile.sh + tools/update_profiles.py"
+    return {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_split": traffic_split,
+            "algorithmic_bytes_per_launch": int(bytes_per_launch),
+            "kernel_ms_avg": round(avg_kernel_s * 1e3, 4), "kernel": "raycast_svo_kernel",
+            "binding_roof": "valu_issue",
+            "note": "exact-parity traversal is bound by VALU issue and by the latency of its dependent chains (DESIGN.md 4), not by "
+                    "HBM: frac is kept on HBM as BASELINE defines it, valu_issue says what the kernel issues",
+            "descriptor_reads": canonical_ctr["descriptor_reads"],
+            "descriptor_reads_note": "SURVEY 8d's canonical count (one untimed frame with empty_boxes = 0); the timed frames use the "
+                                     "tree's empty boxes and read " + str(ctr["descriptor_reads"]) + " descriptors + table cells",
+            "steps": ctr["steps"], "valu_issue": issue, "kernel_instance": kernel_instance(c, sc, args.lights),
+            "tree_state": tree_state(c, first_compute_ms, max_dt / args.steps * 1e3),
+            "pmc_source": pmc_note, "kernel_source_hash": kernel_source_hash()}
 
 
 def metric_name(args, W, H):
