@@ -301,6 +301,63 @@ int vrc_read_hits(vrc_caster *h, int32_t *hits, size_t n_int32);
 #define VRC_HIT_FLAG_SHADOW_HIT  4
 #define VRC_HIT_FLAG_OOB_EXIT    8
 
+/* ---- ray queries --------------------------------------------------------- */
+
+/* What does a ray hit?  Picking (the voxel under the cursor), ground height (a ray straight down), collision and line of
+ * sight, against the scene the handle renders -- also trees that exist only in device memory (vrc_build_shell_terrain,
+ * vrc_build_heightfield), which have no host grid to cast against.
+ *
+ * A query is one ray, 6 floats: origin x, y, z, direction x, y, z.  It steps exactly like the primary ray of a frame whose
+ * camera sits at the origin and whose ray is that direction (kernels/ray_caster_kernel.cl): the set-up of :298-323 without
+ * the table rotation, then the loop of :557-570 -- step first, then test, so the origin voxel is never tested -- with the
+ * frame's stop rule: materials 5 and 6 stop the ray, every other value passes through.  In the SVO branch a solid voxel's
+ * material comes from the attachments when they are assigned, else it is 5.  The branch follows the settings as a frame
+ * does: using_octree != 0 reads the dense map, 0 the tree.
+ *
+ * Two modes (flags):
+ *   VRC_RAY_AS_PIXEL  the frame's own rules: the octree bias of :342-354 is computed for the origin's voxel exactly as a
+ *                     frame computes it for a camera there (setting octree_bias honoured; in both branches, as in a frame),
+ *                     and a direction with a zero component is rejected (:293-294).  Casting a frame's own pixel rays --
+ *                     the viewport table rotated on the host with the frame's sin / cos (vrc_assign_camera_trig) -- gives
+ *                     that frame's hit records: picking returns what the user sees.
+ *   0 (default)       no bias, and zero components are allowed: an axis whose delta_t is +inf (a zero component, or one so
+ *                     small that 1 / d overflows) gets delta_t = t = +inf and never steps.  Ground-height and axis-aligned
+ *                     collision rays need this.
+ * Both modes reject a ray with a non-finite component and a zero direction.
+ *
+ * max_steps caps distance_traveled like the setting max_distance caps a frame's; 0 means no cap below the map's edge (the
+ * kernel bounds a ray at 3 * dim + 3 iterations, dim the largest map side).  Origins are expected in [0, dim)^3; a ray
+ * that starts outside is stepped as a frame's would be -- the bounds test follows each step -- so it leaves on its first
+ * iteration unless that step enters the map.
+ *
+ * out receives 8 x int32 per ray:
+ *   [0..2] the voxel hit, or -1        [3] its material (5 / 6), or 0      [4] face bits of the entering step (bit0 x, bit1 y, bit2 z), or 0
+ *   [5] VRC_RAY_* flags                [6] distance_traveled when the hit block would run (at the exit / the cap for a miss)
+ *   [7] the float bits of min(intersection_t) at the entering iteration, before its increment: the entry parameter along the
+ *       direction (biased under VRC_RAY_AS_PIXEL); for a miss the value at the last iteration; 0 for a rejected ray.
+ * Fields 0-4 and 6 mean what fields 0-4 and 6 of vrc_read_hits mean for a frame rendered with shadow_rays = 0.
+ *
+ * Queries never change what a frame reports: counters, timing, hit records and the image stay those of the last frame.
+ * Both calls are synchronous: they enqueue on the handle's stream (a frame in flight from vrc_compute_async finishes
+ * first) and return when the records are written.  They use the coarse table and the empty boxes when vrc_prepare /
+ * vrc_validate / a frame has built them (trees with box records for the upper levels only use them where they exist), and
+ * otherwise run without them with the same results: a query never starts a derived build.  A group handle queries on
+ * rank 0's GPU (the scene is replicated); the caller's current device is left as it was.  Errors, with nothing launched:
+ * VRC_ERR_INVALID_ARGUMENT for a null handle / pointer, n < 0, max_steps < 0 or unknown flag bits; VRC_ERR_NOT_READY
+ * before a successful vrc_validate or without a scene.  n = 0 succeeds.
+ *
+ * vrc_cast_rays: host arrays (float[6 * n] in, int32[8 * n] out), staged through device buffers that grow on demand and
+ * are freed by vrc_release_map / _octree / _viewport and vrc_destroy.
+ * vrc_cast_rays_device: device pointers on the handle's GPU (a torch tensor's data_ptr(), say), 4-byte aligned.  Work
+ * queued on the null stream before the call is waited for; work on other streams is the caller's to finish first.      */
+#define VRC_RAY_AS_PIXEL 1u
+#define VRC_RAY_HIT       1
+#define VRC_RAY_LEFT_MAP  2
+#define VRC_RAY_STEP_CAP  4
+#define VRC_RAY_REJECTED  8
+int vrc_cast_rays(vrc_caster *h, const float *rays, int64_t n, int32_t max_steps, uint32_t flags, int32_t *out);
+int vrc_cast_rays_device(vrc_caster *h, const void *d_rays, int64_t n, int32_t max_steps, uint32_t flags, void *d_out);
+
 /* Device pointers of the resident frame buffers (float4[w*h], int32[8*w*h]);
  * lets a host that owns the GPU (e.g. a torch process) consume the frame
  * without a PCIe round trip.                                                 */

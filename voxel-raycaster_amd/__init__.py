@@ -158,9 +158,14 @@ SIGNATURES = {
                                           _i32p, C.POINTER(BuildInfo)]),
     "vrc_read_descriptors": (C.c_int, [_H, C.c_uint64, C.c_uint64, _u64p]),
     "vrc_octree_size": (C.c_int, [_H, _u64p, _u64p]),
+    "vrc_cast_rays": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p]),
+    "vrc_cast_rays_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
+# ray queries (vrc_cast_rays): the flag, and the bits of record field 5
+RAY_AS_PIXEL = 1
+RAY_HIT, RAY_LEFT_MAP, RAY_STEP_CAP, RAY_REJECTED = 1, 2, 4, 8
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype = _res
@@ -716,6 +721,24 @@ class CLCaster:
         if not self._ok(lib.vrc_read_hits(self._h, _ptr(out, _i32p), out.size)):
             raise VrcError(self.last_error())
         return out
+
+    # -- ray queries (vrc_cast_rays, include/vrc.h)
+    def cast_rays(self, rays: np.ndarray, max_steps: int = 0, as_pixel: bool = False) -> np.ndarray:
+        """What each ray hits: rays (n, 6) float32 = origin xyz, direction xyz -> (n, 8) int32 records (voxel xyz or -1,
+        material, face bits, RAY_* flags, steps, entry parameter as float bits).  as_pixel: the frame's own rules."""
+        r = np.ascontiguousarray(rays, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise VrcError(f"cast_rays: rays must have shape (n, 6), got {r.shape}")
+        out = np.empty((r.shape[0], 8), dtype=np.int32)
+        if not self._ok(lib.vrc_cast_rays(self._h, _ptr(r, _f32p), r.shape[0], int(max_steps), RAY_AS_PIXEL if as_pixel else 0,
+                                          _ptr(out, _i32p))):
+            raise VrcError(self.last_error())
+        return out
+
+    def cast_rays_device(self, rays_ptr: int, out_ptr: int, n: int, max_steps: int = 0, as_pixel: bool = False) -> bool:
+        """cast_rays on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 6 float32 in, n x 8 int32 out)."""
+        return self._ok(lib.vrc_cast_rays_device(self._h, C.c_void_p(rays_ptr), int(n), int(max_steps), RAY_AS_PIXEL if as_pixel else 0,
+                                                 C.c_void_p(out_ptr)))
 
     def counters(self) -> dict:
         c = Counters()

@@ -1,0 +1,262 @@
+// raycast_query.hip -- batched ray queries against the resident scene (vrc_cast_rays, include/vrc.h) for gfx950.
+//
+// One lane per ray, rays in input order: a query batch is incoherent (picking, ground height, line of sight), so the frame's
+// 8x8 tile mapping and its wave-wide round scheduler buy nothing here.  Each ray runs the primary-ray part of
+// kernels/ray_caster_kernel.cl: the set-up of ray_setup() (raycast_common.hpp) without the table rotation, and the step loop
+// :557-570 (step first, then test: the origin voxel is never tested) with the stop rule of the hit block -- materials 5 and 6
+// stop the ray, every other value passes.  The float recurrence t += delta_t * face_mask is kept step for step, so a query with
+// VRC_RAY_AS_PIXEL reproduces a frame's hit record bit for bit.
+//
+// Traversal (SVO branch): a node event re-descends from the coarse table's cell (or the root) -- stackless, so a lane holds no
+// traversal stack and the kernel no LDS and no scratch.  An empty node is widened to its empty box (empty_boxes.hip's word: the
+// table cell's own, the descriptor's record, or below the levels with records the node widened over its empty siblings ahead of
+// the ray), and the ray crosses it with per-axis countdowns: no memory reads, no bounds tests until a countdown runs out.  Deep
+// inside a box, safe runs (safe_run.hpp) take the iterations without countdowns.  The array branch is a plain DDA over the map.
+#include <hip/hip_runtime.h>
+
+#include "raycast_common.hpp"
+#include "raycast_query.h"
+#include "safe_run.hpp"
+
+namespace vrc {
+
+namespace {
+
+// iterations per safe run: the recovery bound of safe_run.hpp then allows thresholds up to 2^16
+constexpr int kQuerySafeSteps = 64;
+
+// the packed cursor entry of the SVO kernel: bits 0-7 valid mask, 8-15 leaf mask, 16-63 absolute index of the first kept child
+__device__ __forceinline__ uint64_t query_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
+    uint64_t base = index + (d & 0x7fffULL);
+    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
+    return (base << 16) | ((d >> 16) & 0xffffULL);
+}
+
+// frame_setup_kernel's get_oct_vox(camera voxel) bias (ray_caster_kernel.cl:342-354) for a camera at `o`
+__device__ void origin_bias(const QueryParams &q, const float o[3], int bias[3]) {
+    int pos[3], corner[3] = {0, 0, 0};
+    for (int a = 0; a < 3; a++) pos[a] = (int)floorf(o[a]);
+    uint64_t index = q.root_index, d = q.descriptors[index];
+    int dimension = 1 << q.log2_dim, res = dimension / 2;
+    while (dimension > 1) {
+        const int half = dimension / 2;
+        int i = 0;
+        for (int a = 0; a < 3; a++)
+            if (pos[a] >= corner[a] + half) { i |= 1 << a; corner[a] += half; }
+        if (!((d >> (16 + i)) & 1ULL)) break;             // not valid: empty node
+        if ((d >> (24 + i)) & 1ULL) break;                // valid leaf: resolution not halved
+        dimension = half;
+        res /= 2;
+        const int before = __popcll((d >> 16) & ((2ULL << i) - 1ULL)) - 1;
+        const uint64_t base = (d & 0x8000ULL) ? q.descriptors[index + (d & 0x7fffULL)] : index + (d & 0x7fffULL);
+        index = base + (uint64_t)before;
+        d = q.descriptors[index];
+    }
+    for (int a = 0; a < 3; a++) bias[a] = q.octree_bias ? (corner[a] - pos[a]) * res / 2 : 0;
+}
+
+// The node of voxel (x, y, z), inside the map.  Returns b >= 0 when the voxel lies in an empty node of size 2^b, with the
+// per-axis countdowns to the face of its empty box (or of the node widened over empty siblings) on the sides the ray leaves
+// through (`pos` bit a: the ray moves toward +a); -1 when the voxel is solid, with its material (attachments: see vrc.h).
+__device__ int query_locate(const QueryParams &q, int x, int y, int z, unsigned pos, int cnt[3], int &mat) {
+    const int n = q.log2_dim;
+    const bool coarse = q.coarse != nullptr, box = q.boxes != nullptr;
+    const int lc = coarse ? q.coarse_log2 : 0;
+    uint64_t cur, cur_index = q.root_index;
+    int top;
+    uint32_t own = 0;                                     // box: the cell's box word (top < lc) or the record of `cur`'s descriptor
+    if (coarse) {
+        const int csh = n - lc;
+        const uint64_t cell = coarse_index((unsigned)(x >> csh), (unsigned)(y >> csh), (unsigned)(z >> csh), lc);
+        const uint64_t e = q.coarse[cell];
+        if (box) own = q.box_aux[cell];
+        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
+        top = (int)(e >> kCoarseLevelShift);
+    } else {
+        cur = query_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
+        top = 0;
+    }
+    for (int guard = 0; guard <= n; guard++) {            // (n + 1 levels at most: a corrupt tree cannot loop)
+        const int b = n - top - 1;
+        const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+        const unsigned masks = (unsigned)cur & 0xffffu;
+        const unsigned bit = 1u << i;
+        if (!(masks & bit)) {
+            uint32_t w = 0;
+            if (box && top < lc) {
+                w = own;
+            } else if (box && top < q.box_levels) {
+                w = q.boxes[(size_t)own * 8u + (unsigned)i];
+            } else {
+                // the empty child widened over the empty siblings that lie ahead of the ray (the SVO kernel's rule), as a box word:
+                // extent code 1 -- one node size -- on the side the ray leaves through
+                const unsigned valid = masks & 0xffu, ahead = ((unsigned)i ^ pos) & 7u;
+                auto span = [&](unsigned e) -> unsigned { return ((unsigned)(0xFF5533110F050301ULL >> (8u * e)) & 0xffu) << ((unsigned)i & ~e); };
+                auto pair = [&](unsigned e) -> unsigned { return (1u << i) | (1u << ((unsigned)i ^ e)); };
+                unsigned ext = 0;
+                if ((span(ahead) & valid) == 0) ext = ahead;
+                else if ((ahead & 2u) && (pair(2u) & valid) == 0) ext = 2u;
+                else if ((ahead & 1u) && (pair(1u) & valid) == 0) ext = 1u;
+                else if ((ahead & 4u) && (pair(4u) & valid) == 0) ext = 4u;
+                for (unsigned a = 0; a < 3; a++) w |= ((ext >> a) & 1u) << (5u * a + (((pos >> a) & 1u) ? 15u : 0u));
+            }
+            // the node at (v & ~(size - 1)) extended by the word's extents, clamped to the map (the bounds test must see the crossing)
+            const int size = 1 << b, dim = 1 << n;
+            const int v[3] = {x, y, z};
+            for (int a = 0; a < 3; a++) {
+                const bool p = (pos >> a) & 1u;
+                const unsigned c = (w >> (unsigned)(5 * a + (p ? 15 : 0))) & 31u;
+                const int ext = (c < 4u ? (int)c : (int)((4u | (c & 3u)) << ((c >> 2) - 1u))) << b;
+                const int o = v[a] & ~(size - 1);
+                if (p) { const int f = o + size + ext; cnt[a] = (f < dim ? f : dim) - v[a]; }
+                else { const int f = o - ext; cnt[a] = v[a] - ((f > 0 ? f : 0) - 1); }
+            }
+            return b;
+        }
+        if (((masks >> 8) & bit) || b == 0) {
+            mat = 5;
+            if (q.attach_lookup && top == n - 1) {            // only bottom-level descriptors carry materials
+                const uint64_t a = q.attachments[q.attach_lookup[cur_index]];
+                mat = (int)(int8_t)(a >> (8 * ((x & 1) | ((y & 1) << 1) | ((z & 1) << 2))));
+            }
+            return -1;
+        }
+        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
+        const uint64_t child = (cur >> 16) + (uint64_t)rank;
+        if (box) own = q.box_child ? (top + 1 < q.box_levels ? q.box_child[own] + rank : 0u) : (uint32_t)child;
+        cur = query_entry(q.descriptors, child, q.descriptors[child]);
+        cur_index = child;
+        top++;
+    }
+    mat = 5;
+    return -1;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kQueryThreads) void raycast_query_kernel(const QueryParams q) {
+    const int64_t stride = (int64_t)gridDim.x * kQueryThreads;
+    for (int64_t k = (int64_t)blockIdx.x * kQueryThreads + threadIdx.x; k < q.n; k += stride) {
+        const float *ray = q.rays + 6 * k;
+        const float o[3] = {ray[0], ray[1], ray[2]};
+        const float rd[3] = {ray[3], ray[4], ray[5]};
+        int32_t *rec = q.out + 8 * k;
+        const bool as_pixel = (q.flags & kQueryAsPixel) != 0;
+
+        bool finite = true;
+        for (int a = 0; a < 3; a++) finite = finite && isfinite(o[a]) && isfinite(rd[a]);
+        const bool any_zero = rd[0] == 0.0f || rd[1] == 0.0f || rd[2] == 0.0f;
+        const bool all_zero = rd[0] == 0.0f && rd[1] == 0.0f && rd[2] == 0.0f;
+        if (!finite || all_zero || (as_pixel && any_zero)) {   // (:293-294 under AS_PIXEL)
+            rec[0] = rec[1] = rec[2] = -1;
+            rec[3] = rec[4] = 0; rec[5] = kRayRejected; rec[6] = 0; rec[7] = 0;
+            continue;
+        }
+
+        // ray_setup (:298-323, 353-354) without the table rotation
+        int s[3], v[3];
+        float dt[3], t[3];
+        int bias[3] = {0, 0, 0};
+        if (as_pixel) origin_bias(q, o, bias);
+        for (int a = 0; a < 3; a++) {
+            s[a] = isign(rd[a]);
+            const float fl = floorf(o[a]);
+            v[a] = (int)fl;
+            dt[a] = fabsf(1.0f / rd[a]);
+            float it = (dt[a] * (o[a] - fl)) * -(float)s[a];
+            it += dt[a] * -1.0f * (it < 0.0f ? -1.0f : 0.0f);
+            // default mode: an axis whose delta_t is +inf (a zero component, or one so small that 1 / d overflows) never steps
+            if (!as_pixel && dt[a] == INFINITY) it = INFINITY;
+            t[a] = it + (float)bias[a];
+        }
+        const unsigned pos = (s[0] >= 0 ? 1u : 0u) | (s[1] >= 0 ? 2u : 0u) | (s[2] >= 0 ? 4u : 0u);
+        const float min_dt = fminf(fminf(dt[0], dt[1]), dt[2]);
+        const float safe_limit = safe_t_limit(kQuerySafeSteps);
+
+        // countdowns to the face of the known-empty region: a lookup is due when one runs out (1: after every step)
+        int cnt[3] = {1, 1, 1};
+        int mat = 0;
+        const bool inside0 = v[0] >= 0 && v[1] >= 0 && v[2] >= 0 && v[0] < q.map_dim[0] && v[1] < q.map_dim[1] && v[2] < q.map_dim[2];
+        if (q.svo && inside0 && query_locate(q, v[0], v[1], v[2], pos, cnt, mat) < 0) cnt[0] = cnt[1] = cnt[2] = 1;
+
+        int dist = 0, fm = 0, status = kRayStepCap;
+        float m = 0.0f;
+        while (dist < q.cap) {                                                     // :357
+            // safe run: deep inside an empty box the iterations need no countdowns (safe_run.hpp); the gate stays closed for
+            // delta_t < 1 (|d| > 1), for t beyond the recovery bound and for the +inf axes' thresholds
+            if (q.svo && q.cap - dist > kQuerySafeSteps && (cnt[0] | cnt[1] | cnt[2]) > 1) {
+                float T = INFINITY;
+                for (int a = 0; a < 3; a++)
+                    if (dt[a] != INFINITY) T = fminf(T, safe_threshold(t[a], dt[a], (float)cnt[a]));
+                bool ok = true;
+                for (int a = 0; a < 3; a++) ok = ok && t_is_safe(t[a]);         // (a NaN -- AS_PIXEL, subnormal d -- fails it)
+                const SafeGate g = ok ? make_gate(T, fminf(fminf(t[0], t[1]), t[2]), safe_limit, min_dt) : SafeGate();
+                if (g.open) {
+                    const float t0[3] = {t[0], t[1], t[2]};
+                    float taken = 0.0f, alive = 1.0f;
+                    for (int u = 0; u < kQuerySafeSteps && alive != 0.0f; u++) {
+                        const float mm = fminf(fminf(t[0], t[1]), t[2]);
+                        alive = fma_sat(mm, g.neg_b1, g.tb1);
+                        taken += alive;
+                        for (int a = 0; a < 3; a++)
+                            if (dt[a] != INFINITY) t[a] = __builtin_fmaf(dt[a], alive_if_zero(t[a] - mm, alive), t[a]);   // :558-559
+                    }
+                    for (int a = 0; a < 3; a++) {
+                        if (dt[a] == INFINITY) continue;
+                        const int st = (int)safe_steps_taken(t[a], t0[a], rd[a]);
+                        cnt[a] -= st;
+                        v[a] += s[a] * st;                                          // :560
+                    }
+                    dist += (int)taken;                                             // :714
+                    continue;
+                }
+            }
+            m = fminf(fminf(t[0], t[1]), t[2]);
+            const int fx = t[0] <= min_cl(t[1], t[2]), fy = t[1] <= min_cl(t[2], t[0]), fz = t[2] <= min_cl(t[0], t[1]);   // :558
+            // :559 as a select: dt * 0 would be NaN on a +inf axis (for finite dt the two are the same float)
+            if (fx) t[0] += dt[0];
+            if (fy) t[1] += dt[1];
+            if (fz) t[2] += dt[2];
+            v[0] += s[0] * fx; v[1] += s[1] * fy; v[2] += s[2] * fz;              // :560
+            cnt[0] -= fx; cnt[1] -= fy; cnt[2] -= fz;
+            fm = fx | (fy << 1) | (fz << 2);
+            if (cnt[0] == 0 || cnt[1] == 0 || cnt[2] == 0) {
+                if (v[0] >= q.map_dim[0] || v[1] >= q.map_dim[1] || v[2] >= q.map_dim[2] || v[0] < 0 || v[1] < 0 || v[2] < 0) {
+                    status = kRayLeftMap;                                          // :563-568
+                    break;
+                }
+                if (q.svo) {
+                    if (query_locate(q, v[0], v[1], v[2], pos, cnt, mat) < 0) {
+                        if (mat == 5 || mat == 6) { status = kRayHit; break; }    // :575
+                        cnt[0] = cnt[1] = cnt[2] = 1;                              // any other material is passed through
+                    }
+                } else {
+                    // :569 (the reference's index, y stride map_dim[2]; a non-cubic map can put it past the array: read as empty)
+                    const uint64_t idx = (uint64_t)((long)v[0] + (long)q.map_dim[0] * ((long)v[1] + (long)q.map_dim[2] * v[2]));
+                    mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
+                    if (mat == 5 || mat == 6) { status = kRayHit; break; }
+                    cnt[0] = cnt[1] = cnt[2] = 1;                                  // the next step is tested again
+                }
+            }
+            dist++;                                                                // :714
+        }
+        const bool hit = status == kRayHit;
+        rec[0] = hit ? v[0] : -1; rec[1] = hit ? v[1] : -1; rec[2] = hit ? v[2] : -1;
+        rec[3] = hit ? mat : 0;
+        rec[4] = hit ? fm : 0;
+        rec[5] = status;
+        rec[6] = dist;
+        rec[7] = __float_as_int(m);
+    }
+}
+
+hipError_t launch_raycast_query(const QueryParams &q, hipStream_t stream) {
+    (void)hipGetLastError();                 // an error an earlier call left behind is not this launch's
+    if (q.n <= 0) return hipSuccess;
+    const int64_t blocks = (q.n + kQueryThreads - 1) / kQueryThreads;
+    const unsigned grid = (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));   // (larger batches: the lanes loop)
+    hipLaunchKernelGGL(raycast_query_kernel, dim3(grid), dim3(kQueryThreads), 0, stream, q);
+    return hipGetLastError();
+}
+
+}  // namespace vrc

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/vrc.h"
+#include "raycast_query.h"
 #include "vrc_params.h"
 
 namespace vrc {
@@ -41,6 +42,7 @@ hipError_t launch_box_check_cells(const uint64_t *descriptors, uint64_t root_ind
 hipError_t launch_box_check(const uint64_t *descriptors, uint64_t n_records, uint64_t root_index, int n, const uint64_t *pos, const uint64_t *desc_of,
                             const uint32_t *boxes, uint64_t samples, uint64_t seed, unsigned long long *result, hipStream_t stream);
 hipError_t launch_frame_setup(const RaycastParams &p, hipStream_t stream);
+hipError_t launch_raycast_query(const QueryParams &q, hipStream_t stream);
 hipError_t launch_reduce_counters(const unsigned long long *partials, int nblocks, unsigned long long *out,
                                   hipStream_t stream);
 hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
@@ -128,6 +130,7 @@ struct vrc_caster {
     unsigned long long *d_counters = nullptr;
     int32_t *d_frame = nullptr;           // {bias[3], reads}
     unsigned int *wd_flag = nullptr;      // host-mapped: raised by the kernel's round watchdog
+    float *d_query_rays = nullptr; int32_t *d_query_out = nullptr; int64_t query_capacity = 0;   // vrc_cast_rays' staging (rays)
 
     // live (retained) host pointers
     const float *cam_dir = nullptr, *cam_pos = nullptr;
@@ -187,6 +190,18 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
 template <class T>
 void release(T *&p) {
     if (p) { (void)hipFree(p); p = nullptr; }
+}
+
+// vrc_cast_rays' staging buffers (the caller's device is left as it was)
+void release_query_staging(vrc_caster *h) {
+    if (!h->d_query_rays && !h->d_query_out) return;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
+    (void)hipSetDevice(h->device);
+    release(h->d_query_rays); release(h->d_query_out);
+    h->query_capacity = 0;
+    if (cur >= 0) (void)hipSetDevice(cur);
+    (void)hipGetLastError();
 }
 
 // the tree's empty boxes, in either form
@@ -520,6 +535,7 @@ int vrc_destroy(vrc_caster *h) {
     release(h->d_map);
     release(h->d_viewport); release(h->d_image); release(h->d_hits); release(h->d_rgba8); release(h->d_jump_cache); release(h->d_jump_slots); h->jump_slot_count = 0; release(h->d_atlas);
     release(h->d_partials); release(h->d_counters); release(h->d_frame);
+    release_query_staging(h);
     if (h->wd_flag) (void)hipHostFree(h->wd_flag);
     if (h->pinned_stage) (void)hipHostFree(h->pinned_stage);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -546,6 +562,7 @@ int vrc_release_map(vrc_caster *h) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
     if (!h->d_map) return fail(h, VRC_ERR_NOT_FOUND, "release_map: no map assigned");
     release(h->d_map);
+    release_query_staging(h);
     h->map_dim[0] = h->map_dim[1] = h->map_dim[2] = 0;
     h->validated = false;
     FOR_PEERS(h, vrc_release_map(q));
@@ -883,6 +900,7 @@ int vrc_release_octree(vrc_caster *h) {
     if (!h->d_desc) return fail(h, VRC_ERR_NOT_FOUND, "release_octree: no octree assigned");
     for (vrc_caster *q : h->peers) release_tree(q);               // ranks sharing rank 0's arrays must let go first
     release_tree(h);
+    release_query_staging(h);
     return VRC_OK;
 }
 
@@ -907,6 +925,7 @@ int vrc_release_viewport(vrc_caster *h) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
     if (!h->d_viewport) return fail(h, VRC_ERR_NOT_FOUND, "release_viewport: no viewport");
     release(h->d_viewport); release(h->d_image); release(h->d_hits); release(h->d_rgba8); release(h->d_jump_cache); release(h->d_jump_slots); h->jump_slot_count = 0;
+    release_query_staging(h);
     h->width = h->height = h->buffer_rows = 0; h->validated = false;
     FOR_PEERS(h, vrc_release_viewport(q));
     return VRC_OK;
@@ -1625,6 +1644,135 @@ int vrc_timing_get(vrc_caster *h, uint64_t *n_launches, double *total_kernel_ms)
     if (n_launches) *n_launches = h->timed_launches;
     if (total_kernel_ms) *total_kernel_ms = ms;
     return rc;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// batched ray queries (vrc_cast_rays / vrc_cast_rays_device, raycast_query.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the caller's current device, put back on every path out of a query (a group handle's queries run on rank 0's GPU)
+struct DeviceRestore {
+    int dev = -1;
+    DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
+    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
+};
+
+// the argument and readiness checks both calls share; nothing is launched when one fails
+int query_check(vrc_caster *h, const void *rays, int64_t n, int32_t max_steps, uint32_t flags, const void *out, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    if (max_steps < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: max_steps = %d < 0", what, (int)max_steps);
+    if (flags & ~(uint32_t)VRC_RAY_AS_PIXEL) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_RAY_AS_PIXEL));
+    if (n > 0 && (!rays || !out)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null rays or output", what);
+    if (!h->validated) return fail(h, VRC_ERR_NOT_READY, "%s: validate() has not succeeded", what);
+    if (!h->have_octree || !h->tree || !h->tree->d_desc) return fail(h, VRC_ERR_NOT_READY, "%s: no octree assigned", what);
+    const int n2 = log2_exact(setting_or(h, "octree_dimensions", 0));
+    if (n2 < 1 || n2 > vrc::kMaxLevels) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: octree_dimensions must be a power of two in [2, 2^%d]", what, vrc::kMaxLevels);
+    const int64_t root = setting_or(h, "octree_root_index", 0);
+    if (root < 0 || (uint64_t)root >= h->tree->n_desc) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: octree_root_index out of range", what);
+    if (setting_or(h, "using_octree", 0) != 0 && !h->d_map) return fail(h, VRC_ERR_NOT_READY, "%s: dense map not assigned (using_octree != 0 selects the array branch)", what);
+    return VRC_OK;
+}
+
+// device pointers the kernel may dereference: memory of the handle's GPU, managed memory or page-locked host memory
+bool query_pointer_ok(const vrc_caster *h, const void *p) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    (void)hipGetLastError();
+    if (e != hipSuccess) return false;
+    if (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeArray) return a.device == h->device;
+    return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeUnified;
+}
+
+// One launch on the handle's stream (current device: h->device).  The tree's guard is held until the kernel is enqueued, as a
+// frame holds it; the coarse table and the empty boxes are used when vrc_prepare / validate / a frame has built them for this
+// tree, never built here.
+int query_enqueue(vrc_caster *h, const float *d_rays, int64_t n, int32_t max_steps, uint32_t flags, int32_t *d_out) {
+    std::unique_lock<std::mutex> lock(h->tree->guard);
+    mirror_tree(h);
+    vrc::QueryParams q;
+    memset(&q, 0, sizeof(q));
+    q.rays = d_rays; q.out = d_out; q.n = n; q.flags = flags;
+    const bool svo = setting_or(h, "using_octree", 0) == 0;
+    const int n2 = log2_exact(setting_or(h, "octree_dimensions", 0));
+    const uint64_t root = (uint64_t)setting_or(h, "octree_root_index", 0);
+    q.svo = svo ? 1 : 0;
+    q.octree_bias = (int32_t)setting_or(h, "octree_bias", 1);
+    q.descriptors = h->d_desc; q.root_index = root; q.log2_dim = n2;
+    if (svo) {
+        q.map_dim[0] = q.map_dim[1] = q.map_dim[2] = 1 << n2;
+        q.attach_lookup = (h->d_attach_lookup && h->d_attach) ? h->d_attach_lookup : nullptr;
+        q.attachments = q.attach_lookup ? h->d_attach : nullptr;
+    } else {
+        for (int a = 0; a < 3; a++) q.map_dim[a] = h->map_dim[a];
+        q.map = h->d_map;
+        q.map_bytes = (uint64_t)h->map_dim[0] * (uint64_t)h->map_dim[1] * (uint64_t)h->map_dim[2];
+    }
+    // max_steps = 0: no cap below the map's edge -- every iteration steps an axis, so 3 dim + 3 bounds a ray that starts inside
+    const int64_t dim_max = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
+    q.cap = max_steps > 0 ? max_steps : (int32_t)std::min<int64_t>(INT32_MAX, 3 * dim_max + 3);
+    const vrc_tree *t = h->tree.get();
+    if (svo && setting_or(h, "coarse_log2", -1) != 0 && t->d_coarse && t->coarse_root == root && t->coarse_depth == n2 &&
+        t->coarse_log2 >= 1 && t->coarse_log2 <= n2 - 2) {
+        q.coarse = t->d_coarse; q.coarse_log2 = t->coarse_log2;
+        if (setting_or(h, "empty_boxes", -1) != 0 && t->d_boxes && t->d_box_aux && t->box_log2 == t->coarse_log2 && t->box_root == root &&
+            t->box_depth == n2) {
+            q.boxes = t->d_boxes; q.box_aux = t->d_box_aux; q.box_child = t->d_box_child; q.box_levels = t->box_levels;
+        }
+    }
+    HIP_TRY(h, vrc::launch_raycast_query(q, h->stream));
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_cast_rays(vrc_caster *h, const float *rays, int64_t n, int32_t max_steps, uint32_t flags, int32_t *out) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = query_check(h, rays, n, max_steps, flags, out, "cast_rays");
+    if (rc != VRC_OK || n == 0) return rc;
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->query_capacity < n) {                                   // staging grows on demand (freed by the release_* calls, destroy)
+        HIP_TRY(h, hipStreamSynchronize(h->stream));               // (a frame in flight must not lose buffers it does not use anyway)
+        release(h->d_query_rays); release(h->d_query_out);
+        h->query_capacity = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->d_query_rays, sizeof(float) * 6 * (size_t)n));
+        HIP_TRY(h, hipMalloc((void **)&h->d_query_out, sizeof(int32_t) * 8 * (size_t)n));
+        h->query_capacity = n;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_query_rays, rays, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    rc = query_enqueue(h, h->d_query_rays, n, max_steps, flags, h->d_query_out);
+    if (rc != VRC_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_query_out, sizeof(int32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+int vrc_cast_rays_device(vrc_caster *h, const void *d_rays, int64_t n, int32_t max_steps, uint32_t flags, void *d_out) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = query_check(h, d_rays, n, max_steps, flags, d_out, "cast_rays_device");
+    if (rc != VRC_OK || n == 0) return rc;
+    if (((uintptr_t)d_rays & 3u) || ((uintptr_t)d_out & 3u)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "cast_rays_device: rays and output must be 4-byte aligned");
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!query_pointer_ok(h, d_rays) || !query_pointer_ok(h, d_out))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "cast_rays_device: rays and output must be memory the GPU of the handle (device %d) can read and write", h->device);
+    // work the host queued on the null stream (a torch tensor's fill, say) comes first: the handle's stream does not wait for it by itself
+    hipEvent_t ready = nullptr;
+    HIP_TRY(h, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ready, nullptr);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ready, 0);
+    (void)hipEventDestroy(ready);
+    HIP_TRY(h, e);
+    rc = query_enqueue(h, static_cast<const float *>(d_rays), n, max_steps, flags, static_cast<int32_t *>(d_out));
+    if (rc != VRC_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
 }
 
 }  // extern "C"
