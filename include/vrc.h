@@ -358,6 +358,56 @@ int vrc_read_hits(vrc_caster *h, int32_t *hits, size_t n_int32);
 int vrc_cast_rays(vrc_caster *h, const float *rays, int64_t n, int32_t max_steps, uint32_t flags, int32_t *out);
 int vrc_cast_rays_device(vrc_caster *h, const void *d_rays, int64_t n, int32_t max_steps, uint32_t flags, void *d_out);
 
+/* ---- box queries --------------------------------------------------------- */
+
+/* Which voxels does a box overlap?  Map::BoxIntersection (include/map/Map.h:51, "the voxels that a box intersects /
+ * contains"): the collision test of a player's or an object's AABB, the voxels an explosion or a brush touches, the terrain
+ * inside a region -- against the scene the handle renders, device-built trees included.
+ *
+ * A box is 6 floats: origin x, y, z and extent x, y, z (the reference's origin and magnitude).  Per axis it covers the voxels
+ * [lo, hi), lo = floor(o), hi = max(ceil(o + m), lo + 1), with o + m rounded to float32 first: the voxels [v, v + 1) that share
+ * a point with the half-open box [o, o + m).  An axis with m = 0 is the plane at o, which lies in voxel floor(o); a box resting
+ * on a face does not overlap the voxel below it.  The range is clipped to the map ([0, dim)^3 for the tree, map_dim for the
+ * dense map); VRC_BOX_CLIPPED is set when any bound was clipped, and a box wholly outside gets count 0 and CLIPPED (it is not
+ * rejected).  VRC_BOX_REJECTED: a non-finite component, a negative extent, or |o| or |o + m| >= 2^30; such a box is not
+ * examined (count 0, corners -1, nothing listed).
+ *
+ * A voxel counts when its material is non-zero; with VRC_BOX_STOPPING_ONLY only when it is 5 or 6 (what stops a ray, the
+ * rule of vrc_cast_rays).  The material is what a frame's hit test reads for the voxel, and the branch follows using_octree
+ * as the ray queries do: the array branch reads the byte at the frame's index x + dx * (y + dz * z) (an index past the array
+ * reads as empty); the SVO branch finds a voxel solid when it lies in a valid slot whose leaf bit is set, at any level, or in
+ * any valid slot at the bottom level -- a valid leaf above the bottom is a solid cube of the slot's size, counted by volume --
+ * with the attachment byte (int8) as the material for bottom-level descriptors when attachments are assigned, else 5.
+ *
+ * Per box i:
+ *   records[8 i + 0]      VRC_BOX_* flags: ANY (count > 0), TRUNCATED (max_voxels > 0 and count > max_voxels), CLIPPED, REJECTED
+ *   records[8 i + 1..3]   the per-axis minimum of the counted voxels; [4..6] the per-axis maximum (inclusive); -1 when
+ *                         nothing counts (ground height under an AABB is [6], penetration extents without a list)
+ *   records[8 i + 7]      entries written to the list: min(count, max_voxels); 0 for a rejected box
+ *   counts[i]             the exact number of counted voxels (int64)
+ *   voxels                may be null iff max_voxels == 0.  Box i owns entries [i max_voxels, (i + 1) max_voxels), each 4 int32
+ *                         (x, y, z, material): the first min(count, max_voxels) counted voxels in Morton order (key bit 3k = x
+ *                         bit k, 3k + 1 = y bit k, 3k + 2 = z bit k -- the tree's own child-slot order), so truncation is
+ *                         deterministic and a full list is sorted.  Entries past records[8 i + 7] are not written.
+ *
+ * Everything else is as vrc_cast_rays: synchronous on the handle's stream (a frame in flight finishes first); the image, hit
+ * records, counters and timing are untouched; the coarse table is used when vrc_prepare / vrc_validate / a frame has built it
+ * and otherwise the query descends from the root with the same results (a query never starts a derived build); a group
+ * handle queries on rank 0's GPU and the caller's current device is left as it was; the host call's staging and the scratch
+ * of both calls grow on demand and are freed by vrc_release_map / _octree / _viewport and vrc_destroy.  Device pointers must be
+ * memory the handle's GPU can read and write, 4-byte aligned, counts 8-byte aligned.  Errors, with nothing launched:
+ * VRC_ERR_INVALID_ARGUMENT for a null handle or pointer, n < 0, max_voxels < 0, unknown flag bits or misalignment;
+ * VRC_ERR_NOT_READY as for ray queries; VRC_ERR_LIMIT when n * max_voxels * 16 overflows size_t.  n = 0 succeeds.       */
+#define VRC_BOX_STOPPING_ONLY 1u   /* flag: count only materials 5 and 6 (what stops a ray / vrc_cast_rays' rule) */
+#define VRC_BOX_ANY        1       /* record[0] bits */
+#define VRC_BOX_TRUNCATED  2
+#define VRC_BOX_CLIPPED    4
+#define VRC_BOX_REJECTED   8
+int vrc_box_intersection(vrc_caster *h, const float *boxes, int64_t n, int32_t max_voxels, uint32_t flags,
+                         int32_t *records, int64_t *counts, int32_t *voxels);
+int vrc_box_intersection_device(vrc_caster *h, const void *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags,
+                                void *d_records, void *d_counts, void *d_voxels);
+
 /* Device pointers of the resident frame buffers (float4[w*h], int32[8*w*h]);
  * lets a host that owns the GPU (e.g. a torch process) consume the frame
  * without a PCIe round trip.                                                 */

@@ -160,12 +160,17 @@ SIGNATURES = {
     "vrc_octree_size": (C.c_int, [_H, _u64p, _u64p]),
     "vrc_cast_rays": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p]),
     "vrc_cast_rays_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
+    "vrc_box_intersection": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p, C.POINTER(C.c_int64), _i32p]),
+    "vrc_box_intersection_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
 # ray queries (vrc_cast_rays): the flag, and the bits of record field 5
 RAY_AS_PIXEL = 1
 RAY_HIT, RAY_LEFT_MAP, RAY_STEP_CAP, RAY_REJECTED = 1, 2, 4, 8
+# box queries (vrc_box_intersection): the flag, and the bits of record field 0
+BOX_STOPPING_ONLY = 1
+BOX_ANY, BOX_TRUNCATED, BOX_CLIPPED, BOX_REJECTED = 1, 2, 4, 8
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype = _res
@@ -739,6 +744,32 @@ class CLCaster:
         """cast_rays on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 6 float32 in, n x 8 int32 out)."""
         return self._ok(lib.vrc_cast_rays_device(self._h, C.c_void_p(rays_ptr), int(n), int(max_steps), RAY_AS_PIXEL if as_pixel else 0,
                                                  C.c_void_p(out_ptr)))
+
+    # -- box queries (vrc_box_intersection, include/vrc.h)
+    def box_intersection(self, boxes: np.ndarray, max_voxels: int = 0, stopping_only: bool = False):
+        """The voxels each box overlaps: boxes (n, 6) float32 = origin xyz, extent xyz -> (records (n, 8) int32 = BOX_* flags,
+        min xyz, max xyz, entries listed; counts (n,) int64; voxels (n, max_voxels, 4) int32 = x, y, z, material in Morton
+        order, or None for max_voxels = 0).  List entries past records[:, 7] are left as -1."""
+        b = np.ascontiguousarray(boxes, dtype=np.float32)
+        if b.ndim != 2 or b.shape[1] != 6:
+            raise VrcError(f"box_intersection: boxes must have shape (n, 6), got {b.shape}")
+        n = b.shape[0]
+        records = np.empty((n, 8), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int64)
+        voxels = np.full((n, int(max_voxels), 4), -1, dtype=np.int32) if max_voxels > 0 else None
+        if not self._ok(lib.vrc_box_intersection(self._h, _ptr(b, _f32p), n, int(max_voxels), BOX_STOPPING_ONLY if stopping_only else 0,
+                                                 _ptr(records, _i32p), _ptr(counts, C.POINTER(C.c_int64)),
+                                                 _ptr(voxels, _i32p) if voxels is not None else None)):
+            raise VrcError(self.last_error())
+        return records, counts, voxels
+
+    def box_intersection_device(self, boxes_ptr: int, n: int, records_ptr: int, counts_ptr: int, voxels_ptr: int = 0,
+                                max_voxels: int = 0, stopping_only: bool = False) -> bool:
+        """box_intersection on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 6 float32 in, n x 8 int32
+        records, n int64 counts, n x max_voxels x 4 int32 voxels)."""
+        return self._ok(lib.vrc_box_intersection_device(self._h, C.c_void_p(boxes_ptr), int(n), int(max_voxels),
+                                                        BOX_STOPPING_ONLY if stopping_only else 0, C.c_void_p(records_ptr),
+                                                        C.c_void_p(counts_ptr), C.c_void_p(voxels_ptr or None)))
 
     def counters(self) -> dict:
         c = Counters()

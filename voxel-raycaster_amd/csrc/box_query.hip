@@ -1,0 +1,414 @@
+// box_query.hip -- batched box-overlap queries against the resident scene (vrc_box_intersection, include/vrc.h) for gfx950.
+//
+// Count, then emit.  A box's clipped voxel range is covered by aligned nodes of one size 2^s (the items), numbered in Morton
+// order of their node coordinates; s grows with the box's largest side up to 64 voxels, and past that only as far as keeping a
+// box at <= 65 nodes per axis needs, so one huge box is many work items.  Items of <= 4^3 voxels are one lane; larger items
+// are one wave whose 64 lanes take the item's 4 x 4 x 4 sub-cubes (lane id = the sub-cube's Morton index), so a 64^3 item is
+// 64 walks of 16^3, not one lane's serial walk.
+//
+//   box_query_plan_kernel      one lane per box: the range rule, the flags, the item size and count (lane items / wave items)
+//   (inclusive scans of the two item counts over the boxes: each item's global id; rocprim)
+//   box_query_count_kernel     pass 0: each item walks its node restricted to the box; per-box totals and corners by integer atomics
+//                        (sum, min, max: the result does not depend on their order); with a list, each item's count is kept
+//   (emit only: inclusive scan of the item counts -- an item's list offset inside its box)
+//   box_query_count_kernel     pass 1: items whose offset is below max_voxels walk again and write their voxels in Morton order
+//   box_query_finalize_kernel  one lane per box: records and counts, with plain stores
+//
+// The walk (SVO branch) descends from the coarse table's cell (or the root) to the walk's node, then visits the node's subtree
+// in Morton order with a restart at every finished node -- stackless, so no LDS and no scratch.  Empty slots and slots outside
+// the box are skipped; a solid leaf (a valid leaf slot at any level, or any valid slot at the bottom level: query_locate's
+// rule, raycast_query.hip) is counted by volume; a solid cube that the box cuts is entered as a virtual node only to emit, so
+// its first k voxels in Morton order come without visiting the rest.  The array branch walks the same nodes over the map's
+// bytes.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "box_query.h"
+#include "vrc_params.h"
+
+namespace vrc {
+
+namespace {
+
+// the packed cursor entry of raycast_query.hip's query_entry: bits 0-7 valid mask, 8-15 leaf mask, 16-63 index of the first kept child
+__device__ __forceinline__ uint64_t box_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
+    uint64_t base = index + (d & 0x7fffULL);
+    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
+    return (base << 16) | ((d >> 16) & 0xffffULL);
+}
+
+// length of [c, c + s) inside [lo, hi)
+__device__ __forceinline__ int overlap(int c, int s, int lo, int hi) {
+    const int a = c > lo ? c : lo, b = c + s < hi ? c + s : hi;
+    return b > a ? b - a : 0;
+}
+
+// coordinate `axis` of Morton index t (bit 3k + axis -> bit k)
+__device__ __forceinline__ int morton_coord(uint64_t t, int axis) {
+    int v = 0;
+    for (int k = 0; k < 21; k++) v |= (int)((t >> (3 * k + axis)) & 1ULL) << k;
+    return v;
+}
+
+struct Range { int lo[3], hi[3]; };
+struct Acc { int64_t count; int mn[3], mx[3]; };
+
+__device__ __forceinline__ bool counted(const BoxParams &q, int mat) {
+    return (q.flags & kBoxStoppingOnly) ? (mat == 5 || mat == 6) : mat != 0;
+}
+
+// the node of size 2^r at (cx, cy, cz) (r >= 1): 0 empty, 1 inside a solid leaf, 2 a descriptor (cur, its index)
+__device__ int region_descend(const BoxParams &q, int cx, int cy, int cz, int r, uint64_t &cur, uint64_t &cur_index) {
+    const int n = q.log2_dim;
+    int top;
+    cur_index = q.root_index;
+    if (q.coarse && r <= n - q.coarse_log2) {
+        const int csh = n - q.coarse_log2;
+        const uint64_t e = q.coarse[coarse_index((unsigned)(cx >> csh), (unsigned)(cy >> csh), (unsigned)(cz >> csh), q.coarse_log2)];
+        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
+        top = (int)(e >> kCoarseLevelShift);
+    } else {
+        cur = box_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
+        top = 0;
+    }
+    for (int guard = 0; guard <= n && n - top > r; guard++) {
+        const int b = n - top - 1;                        // (>= r >= 1: the child is never a single voxel)
+        const int i = ((cx >> b) & 1) | (((cy >> b) & 1) << 1) | (((cz >> b) & 1) << 2);
+        const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
+        if (!(masks & bit)) return 0;
+        if ((masks >> 8) & bit) return 1;
+        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
+        cur_index = (cur >> 16) + (uint64_t)rank;
+        cur = box_entry(q.descriptors, cur_index, q.descriptors[cur_index]);
+        top++;
+    }
+    return 2;
+}
+
+// Walk the node of size 2^r (r >= 1) at (cx, cy, cz) restricted to the range, in Morton order.  kEmit = false: count and
+// corners into acc.  kEmit = true: write entry base + (voxels counted so far) to `out` while it is below `limit`.
+template <bool kEmit>
+__device__ void walk(const BoxParams &q, int cx, int cy, int cz, int r, const Range &rg, Acc &acc, int64_t base, int64_t limit,
+                     int32_t *__restrict__ out) {
+    uint64_t cur0 = 0, idx0 = 0;
+    const int state0 = q.svo ? region_descend(q, cx, cy, cz, r, cur0, idx0) : 2;
+    if (state0 == 0) return;
+    const uint64_t end = 1ULL << (3 * r);
+    uint64_t p = 0;
+    while (p < end) {
+        // descend from the walk's node toward p (a restart: the node that held p's predecessor is finished)
+        uint64_t cur = cur0, cur_index = idx0;
+        bool solid = state0 == 1;
+        int b = r, ox = cx, oy = cy, oz = cz;
+        while (true) {
+            const int cb = b - 1, s = 1 << cb;
+            const int i = (int)((p >> (3 * cb)) & 7ULL);
+            const int x0 = ox + (i & 1) * s, y0 = oy + ((i >> 1) & 1) * s, z0 = oz + ((i >> 2) & 1) * s;
+            const int wx = overlap(x0, s, rg.lo[0], rg.hi[0]), wy = overlap(y0, s, rg.lo[1], rg.hi[1]), wz = overlap(z0, s, rg.lo[2], rg.hi[2]);
+            if (wx && wy && wz) {
+                int kind = 0, mat = 5;                    // 0 empty, 1 solid, 2 a node to enter
+                uint64_t child = 0;
+                if (!q.svo) {
+                    if (cb > 0) {
+                        kind = 2;
+                    } else {
+                        // the frame's index (y stride map_dim[2]); past the array reads as empty (raycast_query.hip)
+                        const uint64_t idx = (uint64_t)((long)x0 + (long)q.map_dim[0] * ((long)y0 + (long)q.map_dim[2] * z0));
+                        mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
+                        kind = 1;
+                    }
+                } else if (solid) {
+                    kind = 1;
+                } else {
+                    const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
+                    if (masks & bit) {
+                        if (((masks >> 8) & bit) || cb == 0) {
+                            kind = 1;
+                            if (q.attach_lookup && cb == 0) {        // only bottom-level descriptors carry materials
+                                const uint64_t a = q.attachments[q.attach_lookup[cur_index]];
+                                mat = (int)(int8_t)(a >> (8 * i));
+                            }
+                        } else {
+                            kind = 2;
+                            child = (cur >> 16) + (uint64_t)((unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u);
+                        }
+                    }
+                }
+                const bool whole = wx == s && wy == s && wz == s;
+                if (kind == 1 && kEmit && !whole) kind = 3;    // a solid cube the box cuts: entered virtually, to emit in order
+                if (kind >= 2) {
+                    if (kind == 2 && q.svo) {
+                        cur = box_entry(q.descriptors, child, q.descriptors[child]);
+                        cur_index = child;
+                    }
+                    solid = solid || kind == 3;
+                    b = cb; ox = x0; oy = y0; oz = z0;
+                    continue;
+                }
+                if (kind == 1 && counted(q, mat)) {
+                    const int64_t vol = (int64_t)wx * wy * wz;
+                    if (kEmit) {
+                        // (whole: the cube lies in the box) its first voxels in Morton order
+                        const int64_t at = base + acc.count;
+                        const int64_t k = limit - at < vol ? limit - at : vol;
+                        for (int64_t t = 0; t < k; t++) {
+                            int32_t *e = out + 4 * (at + t);
+                            e[0] = x0 + morton_coord((uint64_t)t, 0);
+                            e[1] = y0 + morton_coord((uint64_t)t, 1);
+                            e[2] = z0 + morton_coord((uint64_t)t, 2);
+                            e[3] = mat;
+                        }
+                        acc.count += vol;
+                        if (base + acc.count >= limit) return;
+                    } else {
+                        acc.count += vol;
+                        const int lx = x0 > rg.lo[0] ? x0 : rg.lo[0], ly = y0 > rg.lo[1] ? y0 : rg.lo[1], lz = z0 > rg.lo[2] ? z0 : rg.lo[2];
+                        acc.mn[0] = min(acc.mn[0], lx); acc.mn[1] = min(acc.mn[1], ly); acc.mn[2] = min(acc.mn[2], lz);
+                        acc.mx[0] = max(acc.mx[0], lx + wx - 1); acc.mx[1] = max(acc.mx[1], ly + wy - 1); acc.mx[2] = max(acc.mx[2], lz + wz - 1);
+                    }
+                }
+            }
+            // the child is done: on to its next sibling, or (the last child) restart toward the next node
+            p = ((p >> (3 * cb)) + 1ULL) << (3 * cb);
+            if (i == 7) break;
+        }
+    }
+}
+
+// first box whose inclusive end is above item k
+__device__ int64_t owner(const int64_t *__restrict__ end, int64_t n, int64_t k) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (end[mid] > k) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// the j-th node (Morton order) of the node range [a, b) per axis, in a grid of 2^m nodes per axis
+__device__ void morton_select(int64_t j, const int a[3], const int b[3], int m, int c[3]) {
+    c[0] = c[1] = c[2] = 0;
+    for (int l = m - 1; l >= 0; l--) {
+        const int h = 1 << l;
+        int nx = c[0], ny = c[1], nz = c[2];
+        for (int o = 0; o < 8; o++) {
+            const int x0 = c[0] + (o & 1) * h, y0 = c[1] + ((o >> 1) & 1) * h, z0 = c[2] + ((o >> 2) & 1) * h;
+            const int64_t k = (int64_t)overlap(x0, h, a[0], b[0]) * overlap(y0, h, a[1], b[1]) * overlap(z0, h, a[2], b[2]);
+            nx = x0; ny = y0; nz = z0;
+            if (j < k) break;
+            j -= k;
+        }
+        c[0] = nx; c[1] = ny; c[2] = nz;
+    }
+}
+
+struct ItemRef { int64_t box, first; int node[3]; Range rg; int s; };
+
+__device__ ItemRef locate_item(const BoxParams &q, const int64_t *__restrict__ end, int64_t k, int64_t space_base) {
+    ItemRef it;
+    it.box = owner(end, q.n, k);
+    const int64_t prev = it.box > 0 ? end[it.box - 1] : 0;
+    it.first = space_base + prev;
+    const BoxPlan pl = q.plan[it.box];
+    it.s = pl.s_log2;
+    int a[3], b[3];
+    for (int x = 0; x < 3; x++) {
+        it.rg.lo[x] = pl.lo[x]; it.rg.hi[x] = pl.hi[x];
+        a[x] = pl.lo[x] >> it.s; b[x] = ((pl.hi[x] - 1) >> it.s) + 1;
+    }
+    morton_select(k - prev, a, b, q.space_log2 - it.s, it.node);
+    return it;
+}
+
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_min(int v) {
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__device__ void add_to_box(const BoxParams &q, int64_t box, const Acc &acc) {
+    if (acc.count <= 0) return;
+    atomicAdd((unsigned long long *)&q.acc_count[box], (unsigned long long)acc.count);
+    int32_t *c = q.acc_corner + 6 * box;
+    for (int x = 0; x < 3; x++) { atomicMin(&c[x], acc.mn[x]); atomicMax(&c[3 + x], acc.mx[x]); }
+}
+
+// the list offset of global item g inside its box (whose first item is `first`)
+__device__ __forceinline__ int64_t item_offset(const BoxParams &q, int64_t g, int64_t first) {
+    return (q.item_end[g] - q.item_count[g]) - (q.item_end[first] - q.item_count[first]);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kBoxThreads) void box_query_plan_kernel(const BoxParams q, int64_t *__restrict__ small_cnt, int64_t *__restrict__ big_cnt) {
+    const int64_t stride = (int64_t)gridDim.x * kBoxThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kBoxThreads + threadIdx.x; i < q.n; i += stride) {
+        const float *bx = q.boxes + 6 * i;
+        BoxPlan pl;
+        pl.s_log2 = 1; pl.kind = 0; pl.flags = 0;
+        bool rej = false;
+        float o[3], e[3];
+        for (int a = 0; a < 3; a++) {
+            o[a] = bx[a];
+            const float m = bx[3 + a];
+            e[a] = o[a] + m;                                  // rounded to float32
+            rej = rej || !isfinite(o[a]) || !isfinite(m) || m < 0.0f || !(fabsf(o[a]) < 1073741824.0f) || !(fabsf(e[a]) < 1073741824.0f);
+        }
+        int64_t items = 0;
+        if (rej) {
+            pl.flags = kBoxRejected;
+            for (int a = 0; a < 3; a++) pl.lo[a] = pl.hi[a] = 0;
+        } else {
+            bool empty = false;
+            int L = 1;
+            for (int a = 0; a < 3; a++) {
+                const int lo = (int)floorf(o[a]);
+                int hi = (int)ceilf(e[a]);
+                if (hi < lo + 1) hi = lo + 1;
+                const int dim = q.svo ? (1 << q.log2_dim) : q.map_dim[a];
+                if (lo < 0 || hi > dim) pl.flags |= kBoxClipped;
+                pl.lo[a] = lo > 0 ? lo : 0;
+                pl.hi[a] = hi < dim ? hi : dim;
+                if (pl.lo[a] >= pl.hi[a]) empty = true;
+                else L = max(L, pl.hi[a] - pl.lo[a]);
+            }
+            if (!empty) {
+                const int sl = L <= 1 ? 0 : 32 - __clz(L - 1);     // ceil(log2 L)
+                int s = sl < kBoxMaxItemLog2 ? sl : kBoxMaxItemLog2;
+                if (s < sl - kBoxItemsPerAxisLog2) s = sl - kBoxItemsPerAxisLog2;
+                if (s < 1) s = 1;
+                items = 1;
+                for (int a = 0; a < 3; a++) items *= (int64_t)(((pl.hi[a] - 1) >> s) - (pl.lo[a] >> s) + 1);
+                pl.s_log2 = s;
+                pl.kind = s <= kBoxSmallItemLog2 ? 1 : 2;
+            }
+        }
+        q.plan[i] = pl;
+        small_cnt[i] = pl.kind == 1 ? items : 0;
+        big_cnt[i] = pl.kind == 2 ? items : 0;
+        q.acc_count[i] = 0;
+        int32_t *c = q.acc_corner + 6 * i;
+        c[0] = c[1] = c[2] = INT32_MAX;
+        c[3] = c[4] = c[5] = -1;
+    }
+}
+
+// pass 0: count (and keep per-item counts when q.item_count is set); pass 1: emit
+__global__ __launch_bounds__(kBoxThreads) void box_query_count_kernel(const BoxParams q, int pass) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves_small = (q.n_small + 63) / 64, waves = waves_small + q.n_big;
+    const int64_t wstride = (int64_t)gridDim.x * (kBoxThreads / 64);
+    for (int64_t w = (int64_t)blockIdx.x * (kBoxThreads / 64) + threadIdx.x / 64; w < waves; w += wstride) {
+        if (w < waves_small) {
+            // lane items: one node of 2^s <= 4 voxels per lane
+            const int64_t k = w * 64 + lane;
+            if (k >= q.n_small) continue;
+            const ItemRef it = locate_item(q, q.small_end, k, 0);
+            Acc acc = {0, {INT32_MAX, INT32_MAX, INT32_MAX}, {-1, -1, -1}};
+            const int cx = it.node[0] << it.s, cy = it.node[1] << it.s, cz = it.node[2] << it.s;
+            if (pass == 0) {
+                walk<false>(q, cx, cy, cz, it.s, it.rg, acc, 0, 0, nullptr);
+                add_to_box(q, it.box, acc);
+                if (q.item_count) q.item_count[k] = acc.count;
+            } else if (q.item_count[k] > 0) {
+                const int64_t off = item_offset(q, k, it.first);
+                if (off < q.max_voxels)
+                    walk<true>(q, cx, cy, cz, it.s, it.rg, acc, off, q.max_voxels, q.voxels + (size_t)it.box * (size_t)q.max_voxels * 4u);
+            }
+        } else {
+            // wave items: lane = the Morton index of the item's 4 x 4 x 4 sub-cube of 2^(s-2) voxels
+            const int64_t k = w - waves_small, g = q.n_small + k;
+            const ItemRef it = locate_item(q, q.big_end, k, q.n_small);
+            const int r = it.s - 2;
+            const int cx = (it.node[0] << it.s) + (((lane & 1) | ((lane >> 2) & 2)) << r);
+            const int cy = (it.node[1] << it.s) + ((((lane >> 1) & 1) | ((lane >> 3) & 2)) << r);
+            const int cz = (it.node[2] << it.s) + ((((lane >> 2) & 1) | ((lane >> 4) & 2)) << r);
+            Acc acc = {0, {INT32_MAX, INT32_MAX, INT32_MAX}, {-1, -1, -1}};
+            if (pass == 0) {
+                walk<false>(q, cx, cy, cz, r, it.rg, acc, 0, 0, nullptr);
+                Acc tot;
+                tot.count = wave_sum(acc.count);
+                for (int x = 0; x < 3; x++) { tot.mn[x] = wave_min(acc.mn[x]); tot.mx[x] = wave_max(acc.mx[x]); }
+                if (lane == 0) {
+                    add_to_box(q, it.box, tot);
+                    if (q.item_count) q.item_count[g] = tot.count;
+                }
+            } else {
+                if (q.item_count[g] <= 0) continue;               // (wave-uniform)
+                const int64_t off = item_offset(q, g, it.first);
+                if (off >= q.max_voxels) continue;
+                walk<false>(q, cx, cy, cz, r, it.rg, acc, 0, 0, nullptr);
+                // exclusive prefix of the lanes' counts: lane order is Morton order of the sub-cubes
+                int64_t incl = acc.count;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int64_t v = __shfl_up(incl, o, 64);
+                    if (lane >= o) incl += v;
+                }
+                const int64_t at = off + incl - acc.count;
+                if (acc.count > 0 && at < q.max_voxels) {
+                    Acc e = {0, {0, 0, 0}, {0, 0, 0}};
+                    walk<true>(q, cx, cy, cz, r, it.rg, e, at, q.max_voxels, q.voxels + (size_t)it.box * (size_t)q.max_voxels * 4u);
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBoxThreads) void box_query_finalize_kernel(const BoxParams q) {
+    const int64_t stride = (int64_t)gridDim.x * kBoxThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kBoxThreads + threadIdx.x; i < q.n; i += stride) {
+        const int32_t flags0 = q.plan[i].flags;
+        const int64_t count = (flags0 & kBoxRejected) ? 0 : q.acc_count[i];
+        const int32_t *c = q.acc_corner + 6 * i;
+        int32_t *rec = q.records + 8 * i;
+        int32_t flags = flags0;
+        if (count > 0) flags |= kBoxAny;
+        if (q.max_voxels > 0 && count > q.max_voxels) flags |= kBoxTruncated;
+        rec[0] = flags;
+        for (int x = 0; x < 6; x++) rec[1 + x] = count > 0 ? c[x] : -1;
+        rec[7] = (int32_t)(count < q.max_voxels ? count : q.max_voxels);
+        q.counts[i] = count;
+    }
+}
+
+namespace {
+unsigned grid_for(int64_t threads) {
+    const int64_t blocks = (threads + kBoxThreads - 1) / kBoxThreads;
+    return (unsigned)(blocks < 1 ? 1 : (blocks < (1 << 20) ? blocks : (1 << 20)));   // (larger batches: the lanes loop)
+}
+}  // namespace
+
+hipError_t launch_box_plan(const BoxParams &q, int64_t *small_cnt, int64_t *big_cnt, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(box_query_plan_kernel, dim3(grid_for(q.n)), dim3(kBoxThreads), 0, stream, q, small_cnt, big_cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_box_count(const BoxParams &q, int pass, hipStream_t stream) {
+    (void)hipGetLastError();
+    const int64_t waves = (q.n_small + 63) / 64 + q.n_big;
+    if (waves == 0) return hipSuccess;
+    hipLaunchKernelGGL(box_query_count_kernel, dim3(grid_for(waves * 64)), dim3(kBoxThreads), 0, stream, q, pass);
+    return hipGetLastError();
+}
+
+hipError_t launch_box_finalize(const BoxParams &q, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(box_query_finalize_kernel, dim3(grid_for(q.n)), dim3(kBoxThreads), 0, stream, q);
+    return hipGetLastError();
+}
+
+// inclusive scan of n int64 (rocprim); temp == nullptr: *temp_bytes receives the storage it needs
+hipError_t box_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, int64_t n, hipStream_t stream) {
+    return rocprim::inclusive_scan(temp, *temp_bytes, in, out, (size_t)n, rocprim::plus<int64_t>(), stream);
+}
+
+}  // namespace vrc

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/vrc.h"
+#include "box_query.h"
 #include "raycast_query.h"
 #include "vrc_params.h"
 
@@ -43,6 +44,10 @@ hipError_t launch_box_check(const uint64_t *descriptors, uint64_t n_records, uin
                             const uint32_t *boxes, uint64_t samples, uint64_t seed, unsigned long long *result, hipStream_t stream);
 hipError_t launch_frame_setup(const RaycastParams &p, hipStream_t stream);
 hipError_t launch_raycast_query(const QueryParams &q, hipStream_t stream);
+hipError_t launch_box_plan(const BoxParams &q, int64_t *small_cnt, int64_t *big_cnt, hipStream_t stream);
+hipError_t launch_box_count(const BoxParams &q, int pass, hipStream_t stream);
+hipError_t launch_box_finalize(const BoxParams &q, hipStream_t stream);
+hipError_t box_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, int64_t n, hipStream_t stream);
 hipError_t launch_reduce_counters(const unsigned long long *partials, int nblocks, unsigned long long *out,
                                   hipStream_t stream);
 hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
@@ -131,6 +136,12 @@ struct vrc_caster {
     int32_t *d_frame = nullptr;           // {bias[3], reads}
     unsigned int *wd_flag = nullptr;      // host-mapped: raised by the kernel's round watchdog
     float *d_query_rays = nullptr; int32_t *d_query_out = nullptr; int64_t query_capacity = 0;   // vrc_cast_rays' staging (rays)
+    // vrc_box_intersection: staging of the host call (boxes, records, counts, list), per-box and per-item scratch, scan storage
+    float *d_box_in = nullptr; int32_t *d_box_rec = nullptr; int64_t *d_box_cnt = nullptr; int64_t box_io_capacity = 0;
+    int32_t *d_box_vox = nullptr; size_t box_vox_bytes = 0;
+    void *d_box_plan = nullptr; int64_t *d_box_scan = nullptr; int32_t *d_box_corner = nullptr; int64_t box_capacity = 0;
+    int64_t *d_box_items = nullptr; int64_t box_item_capacity = 0;
+    void *d_box_temp = nullptr; size_t box_temp_bytes = 0;
 
     // live (retained) host pointers
     const float *cam_dir = nullptr, *cam_pos = nullptr;
@@ -192,14 +203,17 @@ void release(T *&p) {
     if (p) { (void)hipFree(p); p = nullptr; }
 }
 
-// vrc_cast_rays' staging buffers (the caller's device is left as it was)
+// vrc_cast_rays' and vrc_box_intersection's staging and scratch buffers (the caller's device is left as it was)
 void release_query_staging(vrc_caster *h) {
-    if (!h->d_query_rays && !h->d_query_out) return;
+    if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp) return;
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) cur = -1;
     (void)hipSetDevice(h->device);
     release(h->d_query_rays); release(h->d_query_out);
     h->query_capacity = 0;
+    release(h->d_box_in); release(h->d_box_rec); release(h->d_box_cnt); release(h->d_box_vox);
+    release(h->d_box_plan); release(h->d_box_scan); release(h->d_box_corner); release(h->d_box_items); release(h->d_box_temp);
+    h->box_io_capacity = 0; h->box_vox_bytes = 0; h->box_capacity = 0; h->box_item_capacity = 0; h->box_temp_bytes = 0;
     if (cur >= 0) (void)hipSetDevice(cur);
     (void)hipGetLastError();
 }
@@ -1770,6 +1784,191 @@ int vrc_cast_rays_device(vrc_caster *h, const void *d_rays, int64_t n, int32_t m
     (void)hipEventDestroy(ready);
     HIP_TRY(h, e);
     rc = query_enqueue(h, static_cast<const float *>(d_rays), n, max_steps, flags, static_cast<int32_t *>(d_out));
+    if (rc != VRC_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// batched box-overlap queries (vrc_box_intersection / vrc_box_intersection_device, box_query.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the argument checks of both calls, then the readiness checks of the ray queries; nothing is launched when one fails
+int box_check(vrc_caster *h, const void *boxes, int64_t n, int32_t max_voxels, uint32_t flags, const void *records, const void *counts,
+              const void *voxels, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    if (max_voxels < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: max_voxels = %d < 0", what, (int)max_voxels);
+    if (flags & ~(uint32_t)VRC_BOX_STOPPING_ONLY)
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_BOX_STOPPING_ONLY));
+    if (n > 0 && (!boxes || !records || !counts)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null boxes, records or counts", what);
+    if (n > 0 && max_voxels > 0 && !voxels) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null voxels with max_voxels = %d", what, (int)max_voxels);
+    if (max_voxels > 0 && (uint64_t)n > SIZE_MAX / 16u / (uint64_t)max_voxels)
+        return fail(h, VRC_ERR_LIMIT, "%s: n * max_voxels * 16 bytes overflows size_t", what);
+    return query_check(h, boxes, n, 0, 0, records, what);
+}
+
+// grow a device buffer to `bytes` (a frame in flight must not lose buffers it does not use anyway: the stream is drained first)
+template <class T>
+int grow(vrc_caster *h, T *&p, size_t &have, size_t bytes) {
+    if (have >= bytes) return VRC_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    release(p);
+    have = 0;
+    HIP_TRY(h, hipMalloc((void **)&p, bytes));
+    have = bytes;
+    return VRC_OK;
+}
+
+// Plan, scans, count, (scan, emit), finalize on the handle's stream (current device: h->device).  The tree's guard is held
+// throughout, as query_enqueue holds it; the coarse table is used when vrc_prepare / validate / a frame has built it for this
+// tree, never built here.  One host wait in the middle: the item totals size the grid and the per-item scratch.
+int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags, int32_t *d_rec, int64_t *d_cnt,
+                int32_t *d_vox) {
+    std::unique_lock<std::mutex> lock(h->tree->guard);
+    mirror_tree(h);
+    vrc::BoxParams q;
+    memset(&q, 0, sizeof(q));
+    q.boxes = d_boxes; q.n = n; q.max_voxels = max_voxels; q.flags = flags;
+    q.records = d_rec; q.counts = d_cnt; q.voxels = max_voxels > 0 ? d_vox : nullptr;
+    const bool svo = setting_or(h, "using_octree", 0) == 0;
+    const int n2 = log2_exact(setting_or(h, "octree_dimensions", 0));
+    const uint64_t root = (uint64_t)setting_or(h, "octree_root_index", 0);
+    q.svo = svo ? 1 : 0;
+    q.descriptors = h->d_desc; q.root_index = root; q.log2_dim = n2;
+    if (svo) {
+        q.map_dim[0] = q.map_dim[1] = q.map_dim[2] = 1 << n2;
+        q.space_log2 = n2;
+        q.attach_lookup = (h->d_attach_lookup && h->d_attach) ? h->d_attach_lookup : nullptr;
+        q.attachments = q.attach_lookup ? h->d_attach : nullptr;
+        const vrc_tree *t = h->tree.get();
+        if (setting_or(h, "coarse_log2", -1) != 0 && t->d_coarse && t->coarse_root == root && t->coarse_depth == n2 &&
+            t->coarse_log2 >= 1 && t->coarse_log2 <= n2 - 2) {
+            q.coarse = t->d_coarse; q.coarse_log2 = t->coarse_log2;
+        }
+    } else {
+        for (int a = 0; a < 3; a++) q.map_dim[a] = h->map_dim[a];
+        q.map = h->d_map;
+        q.map_bytes = (uint64_t)h->map_dim[0] * (uint64_t)h->map_dim[1] * (uint64_t)h->map_dim[2];
+        const int32_t side = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
+        q.space_log2 = 1;
+        while ((1 << q.space_log2) < side) q.space_log2++;
+    }
+    // per-box scratch: plan, the two item counts and their scans, the totals, the corners
+    if (h->box_capacity < n) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        release(h->d_box_plan); release(h->d_box_scan); release(h->d_box_corner);
+        h->box_capacity = 0;
+        HIP_TRY(h, hipMalloc(&h->d_box_plan, sizeof(vrc::BoxPlan) * (size_t)n));
+        HIP_TRY(h, hipMalloc((void **)&h->d_box_scan, sizeof(int64_t) * 5 * (size_t)n));
+        HIP_TRY(h, hipMalloc((void **)&h->d_box_corner, sizeof(int32_t) * 6 * (size_t)n));
+        h->box_capacity = n;
+    }
+    int64_t *small_cnt = h->d_box_scan, *big_cnt = h->d_box_scan + n;
+    q.plan = static_cast<vrc::BoxPlan *>(h->d_box_plan);
+    q.small_end = h->d_box_scan + 2 * n; q.big_end = h->d_box_scan + 3 * n; q.acc_count = h->d_box_scan + 4 * n;
+    q.acc_corner = h->d_box_corner;
+    size_t need = 0;
+    HIP_TRY(h, vrc::box_scan(nullptr, &need, small_cnt, q.small_end, n, h->stream));
+    int rc = grow(h, h->d_box_temp, h->box_temp_bytes, need);
+    if (rc != VRC_OK) return rc;
+    HIP_TRY(h, vrc::launch_box_plan(q, small_cnt, big_cnt, h->stream));
+    size_t bytes = h->box_temp_bytes;
+    HIP_TRY(h, vrc::box_scan(h->d_box_temp, &bytes, small_cnt, q.small_end, n, h->stream));
+    bytes = h->box_temp_bytes;
+    HIP_TRY(h, vrc::box_scan(h->d_box_temp, &bytes, big_cnt, q.big_end, n, h->stream));
+    int64_t totals[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(&totals[0], q.small_end + n - 1, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&totals[1], q.big_end + n - 1, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    q.n_small = totals[0]; q.n_big = totals[1];
+    const int64_t items = q.n_small + q.n_big;
+    const bool emit = max_voxels > 0 && items > 0;
+    if (emit) {
+        // per-item counts and their scan (an item's list offset inside its box)
+        if (h->box_item_capacity < items) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            release(h->d_box_items);
+            h->box_item_capacity = 0;
+            HIP_TRY(h, hipMalloc((void **)&h->d_box_items, sizeof(int64_t) * 2 * (size_t)items));
+            h->box_item_capacity = items;
+        }
+        q.item_count = h->d_box_items; q.item_end = h->d_box_items + items;
+        need = 0;
+        HIP_TRY(h, vrc::box_scan(nullptr, &need, q.item_count, q.item_end, items, h->stream));
+        rc = grow(h, h->d_box_temp, h->box_temp_bytes, need);
+        if (rc != VRC_OK) return rc;
+    }
+    HIP_TRY(h, vrc::launch_box_count(q, 0, h->stream));
+    if (emit) {
+        bytes = h->box_temp_bytes;
+        HIP_TRY(h, vrc::box_scan(h->d_box_temp, &bytes, q.item_count, q.item_end, items, h->stream));
+        HIP_TRY(h, vrc::launch_box_count(q, 1, h->stream));
+    }
+    HIP_TRY(h, vrc::launch_box_finalize(q, h->stream));
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_box_intersection(vrc_caster *h, const float *boxes, int64_t n, int32_t max_voxels, uint32_t flags, int32_t *records,
+                         int64_t *counts, int32_t *voxels) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = box_check(h, boxes, n, max_voxels, flags, records, counts, voxels, "box_intersection");
+    if (rc != VRC_OK || n == 0) return rc;
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->box_io_capacity < n) {                                  // staging grows on demand (freed by the release_* calls, destroy)
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        release(h->d_box_in); release(h->d_box_rec); release(h->d_box_cnt);
+        h->box_io_capacity = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->d_box_in, sizeof(float) * 6 * (size_t)n));
+        HIP_TRY(h, hipMalloc((void **)&h->d_box_rec, sizeof(int32_t) * 8 * (size_t)n));
+        HIP_TRY(h, hipMalloc((void **)&h->d_box_cnt, sizeof(int64_t) * (size_t)n));
+        h->box_io_capacity = n;
+    }
+    const size_t vox_bytes = (size_t)n * (size_t)max_voxels * 16u;
+    if (vox_bytes) {
+        rc = grow(h, h->d_box_vox, h->box_vox_bytes, vox_bytes);
+        if (rc != VRC_OK) return rc;
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_box_in, boxes, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    // the list goes down first: the entries a box does not write come back as the caller left them
+    if (vox_bytes) HIP_TRY(h, hipMemcpyAsync(h->d_box_vox, voxels, vox_bytes, hipMemcpyHostToDevice, h->stream));
+    rc = box_enqueue(h, h->d_box_in, n, max_voxels, flags, h->d_box_rec, h->d_box_cnt, h->d_box_vox);
+    if (rc != VRC_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_box_rec, sizeof(int32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(counts, h->d_box_cnt, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (vox_bytes) HIP_TRY(h, hipMemcpyAsync(voxels, h->d_box_vox, vox_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+int vrc_box_intersection_device(vrc_caster *h, const void *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags, void *d_records,
+                                void *d_counts, void *d_voxels) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = box_check(h, d_boxes, n, max_voxels, flags, d_records, d_counts, d_voxels, "box_intersection_device");
+    if (rc != VRC_OK || n == 0) return rc;
+    const bool list = max_voxels > 0;
+    if (((uintptr_t)d_boxes & 3u) || ((uintptr_t)d_records & 3u) || ((uintptr_t)d_counts & 7u) || (list && ((uintptr_t)d_voxels & 3u)))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "box_intersection_device: boxes, records and voxels must be 4-byte aligned, counts 8-byte aligned");
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!query_pointer_ok(h, d_boxes) || !query_pointer_ok(h, d_records) || !query_pointer_ok(h, d_counts) || (list && !query_pointer_ok(h, d_voxels)))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "box_intersection_device: boxes and outputs must be memory the GPU of the handle (device %d) can read and write", h->device);
+    // work the host queued on the null stream (a torch tensor's fill, say) comes first: the handle's stream does not wait for it by itself
+    hipEvent_t ready = nullptr;
+    HIP_TRY(h, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ready, nullptr);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ready, 0);
+    (void)hipEventDestroy(ready);
+    HIP_TRY(h, e);
+    rc = box_enqueue(h, static_cast<const float *>(d_boxes), n, max_voxels, flags, static_cast<int32_t *>(d_records),
+                     static_cast<int64_t *>(d_counts), static_cast<int32_t *>(d_voxels));
     if (rc != VRC_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return VRC_OK;
