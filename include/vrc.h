@@ -431,6 +431,26 @@ int vrc_get_counters(vrc_caster *h, vrc_counters *out);
  * rendered with the tree's empty boxes and the fields hold that traversal's own, smaller count.  So that one frame's records
  * describe themselves (a host that compares them with the oracle or the reference reads this instead of guessing from settings). */
 int vrc_counters_canonical(vrc_caster *h, int32_t *canonical);
+/* Which kernel rendered the most recent frame of one rank (rank 0 = the handle itself, as in vrc_memory_usage2): the launch
+ * records the template arguments it instantiates the kernel with, so this is what ran, not a second derivation from the
+ * settings.  Size-versioned like vrc_memory2: set struct_size = sizeof(vrc_kernel_info) before the call.
+ * VRC_ERR_INVALID_ARGUMENT for a null handle / pointer or a rank outside the group, VRC_ERR_NOT_READY before the first frame.
+ * A rank that owns no rows of the frame launched nothing: family VRC_KERNEL_NONE, empty name.                              */
+#define VRC_KERNEL_NONE  0
+#define VRC_KERNEL_SVO   1         /* raycast_svo_kernel<kJump, kMulti, kTuned, kLdsRows, kCoarse, kBox>: the exact mode */
+#define VRC_KERNEL_JUMP  2         /* raycast_jump_kernel<kMulti, kCoarse>: stepping_mode 1 */
+#define VRC_KERNEL_ARRAY 3         /* raycast_array_kernel: the dense map, no template arguments */
+typedef struct vrc_kernel_info {
+    uint32_t struct_size;             /* in: sizeof the caller's struct; out: bytes written */
+    int32_t  family;                  /* VRC_KERNEL_* */
+    int32_t  n_args;                  /* template arguments of the instance: 6, 2 or 0 */
+    int32_t  args[6];                 /* their values in declaration order (bools as 0 / 1), -1 past n_args */
+    int32_t  jump_min_run;            /* the frame's resolved threshold of the closed-form jumps; 1 << 24: it ran without them */
+    int32_t  lds_rows;                /* rows of the jumps' Euclid tables in LDS: 3, 2, or 0 (global memory / no jumps) */
+    int32_t  reserved_;
+    char     name[96];                /* e.g. "raycast_svo_kernel<true, false, true, 3, true, true>" */
+} vrc_kernel_info;
+int vrc_last_kernel(vrc_caster *h, int32_t rank, vrc_kernel_info *out);
 
 /* Wave-scheduler statistics of the SVO kernel for the most recent frame (per wave, not per lane):
  * [0] step-loop iterations, [1] bursts, [2] node-event passes, [3] lanes serviced in them,

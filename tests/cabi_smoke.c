@@ -38,6 +38,12 @@ int main(void) {
                 int32_t canonical = -1;
                 if (vrc_counters_canonical(h, &canonical) != VRC_OK || canonical != 1) return 17;
             }
+            {   /* ... and no kernel has rendered one; a rank outside the group is an argument error */
+                vrc_kernel_info k;
+                k.struct_size = (uint32_t)sizeof(k);
+                if (vrc_last_kernel(h, 0, &k) != VRC_ERR_NOT_READY || vrc_last_kernel(h, 1, &k) != VRC_ERR_INVALID_ARGUMENT) return 18;
+                if (vrc_last_kernel(h, 0, NULL) != VRC_ERR_INVALID_ARGUMENT) return 19;
+            }
         }
         {   /* the size-versioned memory report: a caller that knows fewer fields than the library gets only what its struct holds */
             vrc_memory2 m;

@@ -117,3 +117,20 @@ def test_mode_b_budget(kernels):
     k = kernels["_ZN3vrc19raycast_jump_kernelILb0ELb1EEEvNS_13RaycastParamsE"]
     assert k["vgpr_count"] <= 64                       # 8 waves per SIMD
     assert k["private_segment_fixed_size"] <= 48
+
+
+def test_instance_matrix_is_exactly_the_compiled_frame_kernels(kernels):
+    """tests/instance_matrix.py has one row per frame-kernel instance in the code object, and no other: an instance added without a
+    row (tests/test_instances_gpu.py would never launch it on purpose) or a row whose instance is gone fails here, on any machine."""
+    import instance_matrix as im
+    families = ("raycast_svo_kernel", "raycast_jump_kernel", "raycast_array_kernel")
+    built = {n for n in kernels if any(n.startswith(f"_ZN3vrc{len(f)}{f}") for f in families)}
+    rows = {}
+    for r in im.ROWS:
+        assert im.symbol(r) not in rows, f"two rows for {im.name(r)}"
+        rows[im.symbol(r)] = im.name(r)
+    assert all(im.symbol(r) == svo(*r.args) for r in im.ROWS if r.family == "raycast_svo_kernel")       # one mangling rule
+    missing = sorted(built - set(rows))
+    gone = sorted(rows[s] for s in set(rows) - built)
+    assert not missing and not gone, f"compiled instances without a row: {missing}; rows without a compiled instance: {gone}"
+    assert all(len(r.settings) >= 1 and len(r.lights) >= 1 for r in im.ROWS)

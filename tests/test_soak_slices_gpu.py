@@ -50,8 +50,9 @@ def test_soak_slice_exact_jumps_on_small_frames_of_deep_scenes():
     """1500 frames of tests/soak_jumps_gpu.py with a fixed seed: 640x360 frames (900 blocks: fewer than the chip holds,
     the case in which blocks once handed their jump-table slots across XCDs and 1 frame in 4000 came back with a few
     iteration counts off by one) of device-built depth-10 / 12 / 14 / 16 terrains, random poses, 1-4 lights, step caps and
-    jump thresholds, through the empty boxes where the tree has them (depths 10, 12) -- image, hit records and every counter equal
-    to the same frame stepped voxel by voxel from octree node to octree node."""
+    jump thresholds, through the empty boxes, which every one of these trees has (a word per descriptor and child at depths 10, 12
+    and 14, box records for the upper levels at depth 16) -- image, hit records and every counter equal to the same frame stepped
+    voxel by voxel from octree node to octree node."""
     import soak_jumps_gpu
     bad, frames, steps = soak_jumps_gpu.run(budget=150.0, seed=20261002, depths=(10, 12, 14, 16), limit=1500)
     assert frames == 1500 and steps > 1e10

@@ -26,6 +26,17 @@ class VrcError(RuntimeError):
 
 
 def _load() -> C.CDLL:
+    # One HIP runtime per process.  PyTorch-ROCm brings a bundled libamdhip64; a process that loads libvrc.so (which links the
+    # system's) BEFORE torch ends up with both, and in that state hipOccupancyMaxActiveBlocksPerMultiprocessor answers 2 blocks per
+    # CU for every jump instance whatever its LDS size (5 in a process with one runtime): jump_tables_lds_rows then puts the Euclid
+    # tables into global memory and the default depth-12 frame runs <true, *, true, 0, true, true> with threshold 96 instead of the
+    # three-row instance with 16 -- the same pixels, 6-7 % slower (tools/bench_bisect.py; tests/test_instances_gpu.py sees it
+    # through vrc_last_kernel).  bench.py imports torch first for this reason; doing it here makes the order hold for every host
+    # of this package, whenever it imports torch itself.  The import alone does not touch the GPU.
+    try:
+        import torch  # noqa: F401
+    except ImportError:
+        pass
     if not os.path.exists(LIB_PATH):
         raise VrcError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -74,6 +85,11 @@ class Memory2(C.Structure):
         return d
 
 
+class KernelInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("family", C.c_int32), ("n_args", C.c_int32), ("args", C.c_int32 * 6),
+                ("jump_min_run", C.c_int32), ("lds_rows", C.c_int32), ("reserved_", C.c_int32), ("name", C.c_char * 96)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "primary_rays", "shadow_rays", "descriptor_reads", "texel_reads", "map_reads", "steps",
@@ -117,6 +133,7 @@ SIGNATURES = {
     "vrc_device_image": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "vrc_get_counters": (C.c_int, [_H, C.POINTER(Counters)]),
     "vrc_counters_canonical": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "vrc_last_kernel": (C.c_int, [_H, C.c_int32, C.POINTER(KernelInfo)]),
     "vrc_get_scheduler_stats": (C.c_int, [_H, _u64p]),
     "vrc_timing_reset": (C.c_int, [_H]),
     "vrc_timing_get": (C.c_int, [_H, _u64p, C.POINTER(C.c_double)]),
@@ -165,6 +182,7 @@ SIGNATURES = {
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
+KERNEL_NONE, KERNEL_SVO, KERNEL_JUMP, KERNEL_ARRAY = 0, 1, 2, 3      # vrc_last_kernel: family
 # ray queries (vrc_cast_rays): the flag, and the bits of record field 5
 RAY_AS_PIXEL = 1
 RAY_HIT, RAY_LEFT_MAP, RAY_STEP_CAP, RAY_REJECTED = 1, 2, 4, 8
@@ -782,6 +800,16 @@ class CLCaster:
             raise RuntimeError(self.last_error())
         d["canonical_reads"] = bool(canonical.value)
         return d
+
+    def last_kernel(self, rank: int = 0) -> dict:
+        """vrc_last_kernel: the kernel instance the last frame was launched with, as the launch itself recorded it -- family
+        (KERNEL_*), its template arguments, the name as C++ writes it, and the frame's resolved jump_min_run / LDS rows."""
+        k = KernelInfo()
+        k.struct_size = C.sizeof(KernelInfo)
+        if not self._ok(lib.vrc_last_kernel(self._h, rank, C.byref(k))):
+            raise VrcError(self.last_error())
+        return {"family": int(k.family), "args": tuple(int(a) for a in k.args[:k.n_args]), "name": k.name.decode(),
+                "jump_min_run": int(k.jump_min_run), "lds_rows": int(k.lds_rows)}
 
     def scheduler_stats(self) -> dict:
         out = (C.c_uint64 * 8)()

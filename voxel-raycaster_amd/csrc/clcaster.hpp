@@ -138,6 +138,12 @@ public:
         return ok(vrc_read_hits(h_, hits.data(), hits.size()));
     }
 
+    // extension: which kernel instance rendered the last frame (vrc_last_kernel; rank of a group, 0 = this handle)
+    bool last_kernel(vrc_kernel_info &info, int32_t rank = 0) {
+        info.struct_size = (uint32_t)sizeof(info);
+        return ok(vrc_last_kernel(h_, rank, &info));
+    }
+
     int last_status() const { return status_; }
     std::string last_error() const { return h_ ? vrc_last_error(h_) : "not initialised"; }
     vrc_caster *handle() { return h_; }

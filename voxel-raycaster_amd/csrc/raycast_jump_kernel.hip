@@ -391,20 +391,24 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
     publish_counters(p, block_ctr, vals, (int)threadIdx.x);
 }
 
-hipError_t launch_raycast_jump(const RaycastParams &p, hipStream_t stream) {
+hipError_t launch_raycast_jump(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec) {
     (void)hipGetLastError();                 // an error an earlier call left behind is not this launch's
     const int nblocks = p.blocks_x * p.local_tile_rows;
     if (nblocks <= 0) return hipSuccess;
     const int levels = p.log2_dim > 2 ? p.log2_dim - 2 : 1;     // >= the counter partials that reuse the memory
     const size_t lds = (size_t)levels * kBlockThreads * sizeof(uint64_t);
     const bool coarse = p.coarse != nullptr && p.coarse_log2 >= 1 && p.coarse_log2 <= p.log2_dim - 2;
+    // (rec, optional: the instance as vrc_last_kernel reports it, from the same argument list the launch is instantiated with)
+#define VRC_LAUNCH_B(M, C) do { if (rec) { rec->family = kKernelJump; rec->n_args = 2; rec->int_args = 0; rec->args[0] = M; rec->args[1] = C; } \
+                                hipLaunchKernelGGL((raycast_jump_kernel<M, C>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p); } while (0)
     if (coarse) {
-        if (p.light_count > 1) hipLaunchKernelGGL((raycast_jump_kernel<true, true>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p);
-        else hipLaunchKernelGGL((raycast_jump_kernel<false, true>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p);
+        if (p.light_count > 1) VRC_LAUNCH_B(true, true);
+        else VRC_LAUNCH_B(false, true);
     } else {
-        if (p.light_count > 1) hipLaunchKernelGGL((raycast_jump_kernel<true, false>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p);
-        else hipLaunchKernelGGL((raycast_jump_kernel<false, false>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p);
+        if (p.light_count > 1) VRC_LAUNCH_B(true, false);
+        else VRC_LAUNCH_B(false, false);
     }
+#undef VRC_LAUNCH_B
     return hipGetLastError();
 }
 

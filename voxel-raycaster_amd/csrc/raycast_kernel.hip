@@ -1010,7 +1010,7 @@ hipError_t launch_frame_setup(const RaycastParams &p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_raycast_jump(const RaycastParams &p, hipStream_t stream);   // raycast_jump_kernel.hip
+hipError_t launch_raycast_jump(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec);   // raycast_jump_kernel.hip
 
 // dynamic LDS of the SVO kernel: the traversal stack, and behind it the jump tables when they live in LDS
 static bool svo_uses_coarse(const RaycastParams &p) {
@@ -1063,11 +1063,21 @@ int jump_tables_lds_rows(const RaycastParams &p) {
     return cached[slot];
 }
 
-hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream) {
+// the instance a launch names, as the record vrc_last_kernel reports: the parameter list (defaults included) is the kernel's own
+template <bool kJump, bool kMulti, bool kTuned, int kLdsRows = 0, bool kCoarse = false, bool kBox = false>
+static void record_svo_instance(LaunchRecord *rec) {
+    if (!rec) return;
+    rec->family = kKernelSvo; rec->n_args = 6; rec->int_args = 1 << 3;
+    rec->args[0] = kJump; rec->args[1] = kMulti; rec->args[2] = kTuned; rec->args[3] = kLdsRows; rec->args[4] = kCoarse; rec->args[5] = kBox;
+}
+
+// rec (optional): which kernel this launch picked; family kKernelNone when nothing was launched
+hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec) {
     (void)hipGetLastError();                 // an error an earlier call left behind is not this launch's
+    if (rec) { *rec = LaunchRecord{}; rec->jump_min_run = kJumpOff; }
     const int nblocks = p.blocks_x * p.local_tile_rows;
     if (nblocks <= 0) return hipSuccess;
-    if (p.svo && p.stepping_mode == 1) return launch_raycast_jump(p, stream);
+    if (p.svo && p.stepping_mode == 1) return launch_raycast_jump(p, stream, rec);
     if (p.svo) {
         const bool jump = p.jump_min_run < kJumpOff, multi = p.light_count > 1;
         const int lds_rows = jump ? p.jump_tables_lds : 0;       // (vrc_api.cpp has resolved the setting to 0 / 2 / 3 rows with jump_tables_lds_rows)
@@ -1084,10 +1094,13 @@ hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream) {
         // LDS (deep trees); and the same with run-time knobs ONCE each,
         // with the multi-light code compiled in (it renders a single light too -- the relight block never runs): those exist for the
         // tests and tools that move the knobs, and a frame rendered through them is the same frame
-#define VRC_LAUNCH(...) hipLaunchKernelGGL((raycast_svo_kernel<__VA_ARGS__>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p)
+        // (the record is filled from the same argument list the launch is instantiated with)
+#define VRC_LAUNCH(...) do { record_svo_instance<__VA_ARGS__>(rec); \
+                             hipLaunchKernelGGL((raycast_svo_kernel<__VA_ARGS__>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p); } while (0)
 #define VRC_LAUNCH_MT(J, L, ...) do { if (!tuned) VRC_LAUNCH(J, true, false, L, __VA_ARGS__); else if (multi) VRC_LAUNCH(J, true, true, L, __VA_ARGS__); \
                                     else VRC_LAUNCH(J, false, true, L, __VA_ARGS__); } while (0)
         if (jump && !svo_uses_coarse(p)) return hipErrorInvalidValue;     // (vrc_api.cpp switches the jumps off where there is no table)
+        if (rec) { rec->jump_min_run = jump ? p.jump_min_run : kJumpOff; rec->lds_rows = lds_rows; }
         if (svo_uses_boxes(p)) {
             if (lds_rows == 3) VRC_LAUNCH_MT(true, 3, true, true);
             else if (lds_rows == 2) VRC_LAUNCH_MT(true, 2, true, true);
@@ -1103,6 +1116,7 @@ hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream) {
 #undef VRC_LAUNCH_MT
 #undef VRC_LAUNCH
     } else {
+        if (rec) rec->family = kKernelArray;
         hipLaunchKernelGGL(raycast_array_kernel, dim3(nblocks), dim3(kBlockThreads), 0, stream, p);
     }
     return hipGetLastError();

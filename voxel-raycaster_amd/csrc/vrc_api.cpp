@@ -28,7 +28,7 @@
 #include "vrc_params.h"
 
 namespace vrc {
-hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream);
+hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec);
 int jump_tables_lds_rows(const RaycastParams &p);
 hipError_t launch_coarse_build(const uint64_t *descriptors, uint64_t root_index, int log2_dim, int lc, uint64_t *out, hipStream_t stream);
 hipError_t launch_box_positions(const uint64_t *descriptors, uint64_t n_desc, uint64_t root_index, int n, uint64_t *pos, hipStream_t stream);
@@ -123,6 +123,7 @@ struct vrc_caster {
     int32_t peer_access = -1;             // -1 same GPU as rank 0 / rank 0 itself, 1 direct peer access enabled, 0 the runtime stages the copies
     void *pinned_stage = nullptr; size_t pinned_stage_bytes = 0;   // read-back staging for a pageable destination (groups)
     bool last_frame_boxes = false;        // the last enqueued frame was rendered with the tree's empty boxes (its descriptor-read counts are the box traversal's)
+    vrc::LaunchRecord last_launch = {};   // the kernel instance the last enqueued frame was launched with (vrc_last_kernel)
     bool last_frame_wrote_hits = false;   // d_hits belongs to the last enqueued frame (setting hit_records was on)
     uint32_t *d_attach_lookup = nullptr; uint64_t *d_attach = nullptr; uint64_t n_attach = 0;
     float *d_viewport = nullptr; float *d_image = nullptr; int32_t *d_hits = nullptr; uint8_t *d_rgba8 = nullptr;
@@ -1359,7 +1360,7 @@ int compute_async_one(vrc_caster *h) {
 
     HIP_TRY(h, vrc::launch_frame_setup(p, h->stream));
     HIP_TRY(h, hipEventRecord(ev.a, h->stream));
-    HIP_TRY(h, vrc::launch_raycast(p, h->stream));
+    HIP_TRY(h, vrc::launch_raycast(p, h->stream, &h->last_launch));
     HIP_TRY(h, hipEventRecord(ev.b, h->stream));
     h->pending.push_back(ev);
     if (h->pending.size() > 4096) { HIP_TRY(h, hipStreamSynchronize(h->stream)); drain_events(h); }
@@ -1629,6 +1630,31 @@ int vrc_counters_canonical(vrc_caster *h, int32_t *canonical) {
     bool boxes = h->last_frame_boxes;
     for (const vrc_caster *q : h->peers) boxes = boxes || q->last_frame_boxes;
     *canonical = boxes ? 0 : 1;
+    return VRC_OK;
+}
+
+// what launch_raycast recorded for the rank's last enqueued frame, size-versioned like vrc_memory_usage2
+int vrc_last_kernel(vrc_caster *h, int32_t rank, vrc_kernel_info *out) {
+    if (!h || !out || rank < 0 || rank > (int32_t)h->peers.size() || out->struct_size < sizeof(uint32_t)) return VRC_ERR_INVALID_ARGUMENT;
+    const vrc_caster *q = rank == 0 ? h : h->peers[rank - 1];
+    if (!q->frames_enqueued) return fail(h, VRC_ERR_NOT_READY, "last_kernel: no frame computed");
+    const vrc::LaunchRecord &r = q->last_launch;
+    vrc_kernel_info k;
+    memset(&k, 0, sizeof(k));
+    k.family = r.family; k.n_args = r.n_args;
+    for (int i = 0; i < 6; i++) k.args[i] = i < r.n_args ? r.args[i] : -1;
+    k.jump_min_run = r.jump_min_run; k.lds_rows = r.lds_rows;
+    static const char *const family[] = {"", "raycast_svo_kernel", "raycast_jump_kernel", "raycast_array_kernel"};
+    std::string name = family[r.family];
+    for (int i = 0; i < r.n_args; i++) {
+        name += i ? ", " : "<";
+        name += ((r.int_args >> i) & 1) ? std::to_string(r.args[i]) : std::string(r.args[i] ? "true" : "false");
+    }
+    if (r.n_args) name += ">";
+    snprintf(k.name, sizeof(k.name), "%s", name.c_str());
+    const uint32_t n = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(k));
+    k.struct_size = n;
+    memcpy(out, &k, n);
     return VRC_OK;
 }
 

@@ -109,6 +109,15 @@ enum CounterSlot {
     kCtrWaveIters = 8, kCtrBursts, kCtrEventPasses, kCtrEventLanes, kCtrShadePasses, kCtrShadeLanes, kCtrCount = 16
 };
 
+// Which frame kernel a launch picked (vrc_last_kernel): written by launch_raycast / launch_raycast_jump from the template arguments
+// they hand to hipLaunchKernelGGL, never derived from the settings a second time.  int_args: bit i set = argument i is an int
+// (the others are bools); jump_min_run / lds_rows: what the launch ran with (kJumpOff / 0 outside the exact SVO kernel).
+enum KernelFamily { kKernelNone = 0, kKernelSvo = 1, kKernelJump = 2, kKernelArray = 3 };
+struct LaunchRecord {
+    int32_t family, n_args, args[6], int_args;
+    int32_t jump_min_run, lds_rows;
+};
+
 struct RaycastParams {
     // arg 0-1: dense map
     const int8_t *map;
