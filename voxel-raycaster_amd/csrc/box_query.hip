@@ -25,6 +25,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "box_query.h"
+#include "vrc_launch.h"
 #include "vrc_params.h"
 
 namespace vrc {

@@ -29,6 +29,7 @@
 
 #include <chrono>
 
+#include "vrc_launch.h"
 #include "vrc_params.h"
 
 namespace vrc {
@@ -463,10 +464,6 @@ hipError_t launch_box_build(const uint64_t *descriptors, uint64_t n_desc, uint64
     }
     return hipGetLastError();
 }
-
-// What launch_box_build_upper leaves behind (device memory, the caller frees it): records 0 .. count-1 for the descriptors of the
-// levels 0 .. levels-1.
-struct BoxUpper { uint64_t *desc = nullptr, *pos = nullptr; uint32_t *child = nullptr, *boxes = nullptr; uint64_t count = 0; int levels = 0; };
 
 // max_records: the budget (52 bytes of device memory each while building, 36 after the caller frees desc / pos -- or keeps them for
 // vrc_empty_boxes_check); max_levels: 0 = as many as the budget reaches.  Synchronises the stream (one count per level comes back).

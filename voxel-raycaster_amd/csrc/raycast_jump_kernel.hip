@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "raycast_common.hpp"
+#include "vrc_launch.h"
 
 namespace vrc {
 

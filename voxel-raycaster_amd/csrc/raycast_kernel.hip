@@ -37,6 +37,7 @@
 #include "exact_jump.hpp"
 #include "raycast_common.hpp"
 #include "safe_run.hpp"
+#include "vrc_launch.h"
 
 #ifndef VRC_RELIGHT_THRESHOLD
 #define VRC_RELIGHT_THRESHOLD 64      // lanes that must wait for the next light before a wave with stepping lanes serves them
@@ -1009,8 +1010,6 @@ hipError_t launch_frame_setup(const RaycastParams &p, hipStream_t stream) {
     hipLaunchKernelGGL(frame_setup_kernel, dim3(1), dim3(64), 0, stream, p);
     return hipGetLastError();
 }
-
-hipError_t launch_raycast_jump(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec);   // raycast_jump_kernel.hip
 
 // dynamic LDS of the SVO kernel: the traversal stack, and behind it the jump tables when they live in LDS
 static bool svo_uses_coarse(const RaycastParams &p) {

@@ -17,6 +17,7 @@
 #include "raycast_common.hpp"
 #include "raycast_query.h"
 #include "safe_run.hpp"
+#include "vrc_launch.h"
 
 namespace vrc {
 

@@ -33,6 +33,7 @@
 
 #include "../../include/vrc.h"
 #include "shell_scene.hpp"
+#include "vrc_launch.h"
 
 namespace vrc {
 

@@ -17,6 +17,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -25,44 +26,45 @@
 #include "../../include/vrc.h"
 #include "box_query.h"
 #include "raycast_query.h"
+#include "vrc_launch.h"
 #include "vrc_params.h"
 
-namespace vrc {
-hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec);
-int jump_tables_lds_rows(const RaycastParams &p);
-hipError_t launch_coarse_build(const uint64_t *descriptors, uint64_t root_index, int log2_dim, int lc, uint64_t *out, hipStream_t stream);
-hipError_t launch_box_positions(const uint64_t *descriptors, uint64_t n_desc, uint64_t root_index, int n, uint64_t *pos, hipStream_t stream);
-hipError_t box_queries_cut(unsigned long long *out);
-struct BoxUpper { uint64_t *desc = nullptr, *pos = nullptr; uint32_t *child = nullptr, *boxes = nullptr; uint64_t count = 0; int levels = 0; };
-hipError_t launch_box_build_upper(const uint64_t *descriptors, uint64_t root_index, int n, int lc, uint64_t max_records, int max_levels,
-                                  BoxUpper *out, uint32_t *aux, hipStream_t stream);
-hipError_t launch_box_build(const uint64_t *descriptors, uint64_t n_desc, uint64_t root_index, int n, int lc, uint64_t *pos_tmp,
-                            uint32_t *boxes, uint32_t *aux, hipStream_t stream);
-hipError_t launch_box_check_cells(const uint64_t *descriptors, uint64_t root_index, int n, int lc, const uint32_t *aux, uint64_t samples,
-                                  uint64_t seed, unsigned long long *result, hipStream_t stream);
-hipError_t launch_box_check(const uint64_t *descriptors, uint64_t n_records, uint64_t root_index, int n, const uint64_t *pos, const uint64_t *desc_of,
-                            const uint32_t *boxes, uint64_t samples, uint64_t seed, unsigned long long *result, hipStream_t stream);
-hipError_t launch_frame_setup(const RaycastParams &p, hipStream_t stream);
-hipError_t launch_raycast_query(const QueryParams &q, hipStream_t stream);
-hipError_t launch_box_plan(const BoxParams &q, int64_t *small_cnt, int64_t *big_cnt, hipStream_t stream);
-hipError_t launch_box_count(const BoxParams &q, int pass, hipStream_t stream);
-hipError_t launch_box_finalize(const BoxParams &q, hipStream_t stream);
-hipError_t box_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, int64_t n, hipStream_t stream);
-hipError_t launch_reduce_counters(const unsigned long long *partials, int nblocks, unsigned long long *out,
-                                  hipStream_t stream);
-hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
-hipError_t launch_pack_rgba8(const float *image, uint8_t *out, size_t n_pixels, hipStream_t stream);
-int build_shell_terrain_device(hipStream_t stream, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
-                               uint32_t flags, uint64_t validate_samples, const int32_t *probe_xy, uint32_t n_probe,
-                               int32_t *probe_lohi, uint64_t **d_desc, vrc_build_info *out, std::string &error);
-int build_columns_device(hipStream_t stream, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
-                         const uint16_t *host_hi, const uint16_t *host_lo,
-                         uint32_t flags, uint64_t validate_samples, const int32_t *probe_xy, uint32_t n_probe,
-                         int32_t *probe_lohi, uint64_t **d_desc, vrc_build_info *out, std::string &error);
-int build_grid_device(hipStream_t stream, uint32_t depth, const int8_t *host_grid, const int8_t *resident_grid, uint32_t flags,
-                      uint64_t validate_samples, uint64_t **d_desc, uint32_t **d_lookup, uint64_t **d_attach, uint64_t *n_attach,
-                      vrc_build_info *out, std::string &error);
-}  // namespace vrc
+namespace {
+
+// the caller's current device, put back on every path out of the scope (a group handle works on rank 0's GPU; a group that lets
+// go of its peers' trees goes on allocating there)
+struct DeviceRestore {
+    int dev = -1;
+    DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
+    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
+};
+
+template <class T>
+void release(T *&p) {
+    if (p) { (void)hipFree(p); p = nullptr; }
+}
+
+// What a structure derived from a tree was built for, or failed to be built for: the table's level, the root, the tree's depth ...
+struct TableKey {
+    int log2 = 0; uint64_t root = 0; int depth = 0;
+    bool operator==(const TableKey &o) const { return log2 == o.log2 && root == o.root && depth == o.depth; }
+};
+// ... and for the boxes their form (box_mode) and the levels and records asked for.  (A FAILURE is remembered without the last
+// two: they stay 0 in its key.)
+struct BoxKey {
+    TableKey at; int mode = 0; int64_t levels_asked = 0, records_asked = 0;
+    bool operator==(const BoxKey &o) const { return at == o.at && mode == o.mode && levels_asked == o.levels_asked && records_asked == o.records_asked; }
+};
+// An allocation failed: the frames go on without the structure.  Not retried every frame -- but retried as soon as what was
+// asked for changes (level, root, depth) or the host sets coarse_log2 / empty_boxes again (vrc_setting_add / _set)
+template <class Key>
+struct Derived {
+    Key built, failed;
+    bool gave_up = false;
+    std::string note;                                     // why (cleared when the structure is built after all)
+};
+
+}  // namespace
 
 struct vrc_setting { std::string name, define; int64_t value; };
 
@@ -77,33 +79,20 @@ struct vrc_tree {
     uint32_t *d_attach_lookup = nullptr; uint64_t *d_attach = nullptr; uint64_t n_attach = 0;
     // derived, built on first use by whichever handle needs them first (guard: handles of several host threads)
     std::mutex guard;
-    uint64_t *d_coarse = nullptr; uint64_t coarse_root = 0; int coarse_depth = 0, coarse_log2 = 0;
-    uint32_t *d_boxes = nullptr, *d_box_aux = nullptr; uint64_t box_root = 0; int box_depth = 0, box_log2 = 0; double box_build_seconds = 0.0;
+    uint64_t *d_coarse = nullptr; Derived<TableKey> coarse;
+    uint32_t *d_boxes = nullptr, *d_box_aux = nullptr; Derived<BoxKey> boxes; double box_build_seconds = 0.0;
     unsigned long long box_queries_cut = 0;               // region queries of the build that gave up at their budget (boxes smaller than they could be)
     // box records: one per descriptor (box_mode 1: record = descriptor index) or for the upper levels only (box_mode 2: breadth-first
     // records, d_box_child = first-child record, d_box_desc / d_box_pos = descriptor and position of a record, kept for the self-check)
-    int box_mode = 0, box_levels = 0, box_fail_mode = 0; int64_t box_levels_asked = 0, box_records_asked = 0; uint64_t box_records = 0;
+    int box_levels = 0; uint64_t box_records = 0;
     uint32_t *d_box_child = nullptr; uint64_t *d_box_desc = nullptr, *d_box_pos = nullptr;
-    // an allocation failed: the frames go on without the structure.  Not retried every frame -- but retried as soon as what was
-    // asked for changes (level, root, depth) or the host sets coarse_log2 / empty_boxes again (vrc_setting_add / _set)
-    bool coarse_gave_up = false, boxes_gave_up = false;
-    uint64_t coarse_fail_root = 0, box_fail_root = 0; int coarse_fail_depth = 0, coarse_fail_log2 = 0, box_fail_depth = 0, box_fail_log2 = 0;
-    std::string coarse_note, box_note;                    // why (cleared when the structure is built after all)
     ~vrc_tree() {
-        // (the caller's current device is left as it was: a group that lets go of its peers' trees goes on allocating on rank 0's GPU)
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-        (void)hipSetDevice(device);
-        if (d_coarse) (void)hipFree(d_coarse);
-        if (d_boxes) (void)hipFree(d_boxes);
-        if (d_box_aux) (void)hipFree(d_box_aux);
-        if (d_box_child) (void)hipFree(d_box_child);
-        if (d_box_desc) (void)hipFree(d_box_desc);
-        if (d_box_pos) (void)hipFree(d_box_pos);
-        if (d_desc) (void)hipFree(d_desc);
-        if (d_attach_lookup) (void)hipFree(d_attach_lookup);
-        if (d_attach) (void)hipFree(d_attach);
-        if (cur >= 0) (void)hipSetDevice(cur);
+        {
+            DeviceRestore restore;
+            (void)hipSetDevice(device);
+            release(d_coarse); release(d_boxes); release(d_box_aux); release(d_box_child); release(d_box_desc); release(d_box_pos);
+            release(d_desc); release(d_attach_lookup); release(d_attach);
+        }
         (void)hipGetLastError();
     }
 };
@@ -115,9 +104,8 @@ struct vrc_caster {
 
     // scene buffers (device)
     int8_t *d_map = nullptr; int32_t map_dim[3] = {0, 0, 0};
-    // the tree (shared, see vrc_tree); d_desc / n_desc / d_attach* mirror its fields for the code that reads them
+    // the tree (shared, see vrc_tree), attached only once it is complete: "has an octree" is tree != nullptr
     std::shared_ptr<vrc_tree> tree;
-    uint64_t *d_desc = nullptr; uint64_t n_desc = 0; bool have_octree = false;
     bool owns_desc = true;                // false: the tree is another handle's too (a group rank on rank 0's GPU, vrc_assign_octree_from)
     bool own_copy = false;                // group flag VRC_GROUP_OWN_COPIES: never share, always take the device-to-device copy path
     int32_t peer_access = -1;             // -1 same GPU as rank 0 / rank 0 itself, 1 direct peer access enabled, 0 the runtime stages the copies
@@ -125,7 +113,6 @@ struct vrc_caster {
     bool last_frame_boxes = false;        // the last enqueued frame was rendered with the tree's empty boxes (its descriptor-read counts are the box traversal's)
     vrc::LaunchRecord last_launch = {};   // the kernel instance the last enqueued frame was launched with (vrc_last_kernel)
     bool last_frame_wrote_hits = false;   // d_hits belongs to the last enqueued frame (setting hit_records was on)
-    uint32_t *d_attach_lookup = nullptr; uint64_t *d_attach = nullptr; uint64_t n_attach = 0;
     float *d_viewport = nullptr; float *d_image = nullptr; int32_t *d_hits = nullptr; uint8_t *d_rgba8 = nullptr;
     uint32_t *d_jump_cache = nullptr, *d_jump_slots = nullptr; int jump_slot_count = 0;   // Euclid tables of the exact closed-form jumps (exact_jump.hpp), per resident block
     int32_t width = 0, height = 0;
@@ -189,6 +176,13 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
         }                                                                                         \
     } while (0)
 
+// a step that reports through the handle's own error text: its failure is the caller's
+#define VRC_TRY(...)                                                                              \
+    do {                                                                                          \
+        const int rc_ = (__VA_ARGS__);                                                            \
+        if (rc_ != VRC_OK) return rc_;                                                            \
+    } while (0)
+
 // replicate a call on every other rank of a group; the first failure is reported through rank 0
 #define FOR_PEERS(h, expr)                                                                        \
     do {                                                                                          \
@@ -199,51 +193,58 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
         }                                                                                         \
     } while (0)
 
-template <class T>
-void release(T *&p) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-}
-
 // vrc_cast_rays' and vrc_box_intersection's staging and scratch buffers (the caller's device is left as it was)
 void release_query_staging(vrc_caster *h) {
     if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp) return;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) cur = -1;
-    (void)hipSetDevice(h->device);
-    release(h->d_query_rays); release(h->d_query_out);
-    h->query_capacity = 0;
-    release(h->d_box_in); release(h->d_box_rec); release(h->d_box_cnt); release(h->d_box_vox);
-    release(h->d_box_plan); release(h->d_box_scan); release(h->d_box_corner); release(h->d_box_items); release(h->d_box_temp);
-    h->box_io_capacity = 0; h->box_vox_bytes = 0; h->box_capacity = 0; h->box_item_capacity = 0; h->box_temp_bytes = 0;
-    if (cur >= 0) (void)hipSetDevice(cur);
+    {
+        DeviceRestore restore;
+        (void)hipSetDevice(h->device);
+        release(h->d_query_rays); release(h->d_query_out);
+        h->query_capacity = 0;
+        release(h->d_box_in); release(h->d_box_rec); release(h->d_box_cnt); release(h->d_box_vox);
+        release(h->d_box_plan); release(h->d_box_scan); release(h->d_box_corner); release(h->d_box_items); release(h->d_box_temp);
+        h->box_io_capacity = 0; h->box_vox_bytes = 0; h->box_capacity = 0; h->box_item_capacity = 0; h->box_temp_bytes = 0;
+    }
     (void)hipGetLastError();
+}
+
+// what create_viewport allocates and a frame adds to it
+void release_viewport_buffers(vrc_caster *h) {
+    release(h->d_viewport); release(h->d_image); release(h->d_hits); release(h->d_rgba8); release(h->d_jump_cache); release(h->d_jump_slots);
+    h->jump_slot_count = 0;
 }
 
 // the tree's empty boxes, in either form
 void release_boxes(vrc_tree *t) {
     release(t->d_boxes); release(t->d_box_aux); release(t->d_box_child); release(t->d_box_desc); release(t->d_box_pos);
-    t->box_log2 = 0; t->box_mode = 0; t->box_records = 0; t->box_levels = 0;
+    t->boxes.built = BoxKey{}; t->box_records = 0; t->box_levels = 0;
 }
 
 // the handle lets go of its tree; the arrays, the table and the boxes are freed with the last handle that holds them
 void release_tree(vrc_caster *h) {
     h->tree.reset();
-    h->d_desc = nullptr; h->d_attach_lookup = nullptr; h->d_attach = nullptr;
     h->owns_desc = true;
-    h->n_desc = 0; h->n_attach = 0; h->have_octree = false; h->validated = false;
+    h->validated = false;
 }
-// a fresh, unshared tree for this handle (its arrays are filled in by the caller)
-vrc_tree *new_tree(vrc_caster *h) {
-    h->tree = std::make_shared<vrc_tree>();
-    h->tree->device = h->device;
-    h->owns_desc = true;
-    return h->tree.get();
+// ... and so does its whole group: the peers first (ranks sharing rank 0's arrays must let go before rank 0 does).  Called BEFORE a
+// new tree is built or uploaded: the old one must be gone by then (trees of BASELINE configs[4]'s size do not fit twice), and a
+// new tree never inherits the old one's materials
+void drop_trees(vrc_caster *h) {
+    for (vrc_caster *q : h->peers) release_tree(q);
+    release_tree(h);
 }
-// the handle's mirrors of its tree's fields
-void mirror_tree(vrc_caster *h) {
-    const vrc_tree *t = h->tree.get();
-    h->d_desc = t ? t->d_desc : nullptr; h->n_desc = t ? t->n_desc : 0;
-    h->d_attach_lookup = t ? t->d_attach_lookup : nullptr; h->d_attach = t ? t->d_attach : nullptr; h->n_attach = t ? t->n_attach : 0;
+// a fresh tree on this GPU, held by nobody yet: the caller fills it and attaches it only once it is complete (install_tree), so a
+// step that fails on the way just lets it go
+std::shared_ptr<vrc_tree> new_tree(int device, uint64_t *d_desc = nullptr, uint64_t n_desc = 0) {
+    std::shared_ptr<vrc_tree> t = std::make_shared<vrc_tree>();
+    t->device = device; t->d_desc = d_desc; t->n_desc = n_desc;
+    return t;
+}
+// materials are bound as a pair or not at all (the parameter structs name the two fields alike); the caller holds t->guard
+template <class P>
+void bind_attachments(const vrc_tree *t, P &p) {
+    p.attach_lookup = (t->d_attach_lookup && t->d_attach) ? t->d_attach_lookup : nullptr;
+    p.attachments = p.attach_lookup ? t->d_attach : nullptr;
 }
 
 int prepare_one(vrc_caster *h);           // (below, beside the launch path that shares derive_from_tree with it)
@@ -265,7 +266,7 @@ void retry_derived(vrc_caster *h, const char *name) {
     if (!h->tree || (strcmp(name, "coarse_log2") != 0 && strcmp(name, "empty_boxes") != 0 && strcmp(name, "empty_box_records") != 0 &&
                      strcmp(name, "empty_box_levels") != 0)) return;
     std::lock_guard<std::mutex> lock(h->tree->guard);
-    h->tree->coarse_gave_up = h->tree->boxes_gave_up = false;
+    h->tree->coarse.gave_up = h->tree->boxes.gave_up = false;
 }
 
 int set_setting(vrc_caster *h, const char *name, const char *define, int64_t value) {
@@ -331,7 +332,7 @@ void reference_table_row(int32_t width, int32_t height, int32_t row, float *out)
 // table == nullptr: the reference's own table
 int install_viewport(vrc_caster *h, int32_t width, int32_t height, const float *table) {
     HIP_TRY(h, hipSetDevice(h->device));
-    release(h->d_viewport); release(h->d_image); release(h->d_hits); release(h->d_rgba8); release(h->d_jump_cache); release(h->d_jump_slots); h->jump_slot_count = 0;
+    release_viewport_buffers(h);
     h->width = width; h->height = height;
     h->buffer_rows = h->sliced ? local_row_count(h) : height;
     h->validated = false;
@@ -548,7 +549,7 @@ int vrc_destroy(vrc_caster *h) {
     for (auto &p : h->pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     release_tree(h);
     release(h->d_map);
-    release(h->d_viewport); release(h->d_image); release(h->d_hits); release(h->d_rgba8); release(h->d_jump_cache); release(h->d_jump_slots); h->jump_slot_count = 0; release(h->d_atlas);
+    release_viewport_buffers(h); release(h->d_atlas);
     release(h->d_partials); release(h->d_counters); release(h->d_frame);
     release_query_staging(h);
     if (h->wd_flag) (void)hipHostFree(h->wd_flag);
@@ -591,7 +592,7 @@ namespace {
 // Give every other rank of the group rank 0's tree: shared when the rank sits on the same GPU, copied device to
 // device otherwise (hipMemcpyPeerAsync: xGMI, no host staging; SURVEY 8e "peer fan-out").
 int fan_out_tree(vrc_caster *h) {
-    mirror_tree(h);
+    const vrc_tree *s = h->tree.get();
     if (!h->peers.empty()) {                                   // the copies run on the peers' streams: rank 0's tree must be complete
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -604,28 +605,35 @@ int fan_out_tree(vrc_caster *h) {
             q->owns_desc = false;
         } else {
             HIP_TRY(h, hipSetDevice(q->device));
-            vrc_tree *t = new_tree(q);
-            t->n_desc = h->n_desc;
-            HIP_TRY(h, hipMalloc((void **)&t->d_desc, h->n_desc * sizeof(uint64_t)));
-            HIP_TRY(h, hipMemcpyPeerAsync(t->d_desc, q->device, h->d_desc, h->device, h->n_desc * sizeof(uint64_t), q->stream));
-            if (h->d_attach_lookup && h->d_attach) {
-                t->n_attach = h->n_attach;
-                HIP_TRY(h, hipMalloc((void **)&t->d_attach_lookup, h->n_desc * sizeof(uint32_t)));
-                HIP_TRY(h, hipMalloc((void **)&t->d_attach, std::max<uint64_t>(h->n_attach, 1) * sizeof(uint64_t)));
-                HIP_TRY(h, hipMemcpyPeerAsync(t->d_attach_lookup, q->device, h->d_attach_lookup, h->device, h->n_desc * sizeof(uint32_t), q->stream));
-                HIP_TRY(h, hipMemcpyPeerAsync(t->d_attach, q->device, h->d_attach, h->device,
-                                              std::max<uint64_t>(h->n_attach, 1) * sizeof(uint64_t), q->stream));
+            std::shared_ptr<vrc_tree> t = new_tree(q->device);
+            t->n_desc = s->n_desc;
+            HIP_TRY(h, hipMalloc((void **)&t->d_desc, s->n_desc * sizeof(uint64_t)));
+            HIP_TRY(h, hipMemcpyPeerAsync(t->d_desc, q->device, s->d_desc, h->device, s->n_desc * sizeof(uint64_t), q->stream));
+            if (s->d_attach_lookup && s->d_attach) {
+                t->n_attach = s->n_attach;
+                HIP_TRY(h, hipMalloc((void **)&t->d_attach_lookup, s->n_desc * sizeof(uint32_t)));
+                HIP_TRY(h, hipMalloc((void **)&t->d_attach, std::max<uint64_t>(s->n_attach, 1) * sizeof(uint64_t)));
+                HIP_TRY(h, hipMemcpyPeerAsync(t->d_attach_lookup, q->device, s->d_attach_lookup, h->device, s->n_desc * sizeof(uint32_t), q->stream));
+                HIP_TRY(h, hipMemcpyPeerAsync(t->d_attach, q->device, s->d_attach, h->device,
+                                              std::max<uint64_t>(s->n_attach, 1) * sizeof(uint64_t), q->stream));
             }
+            q->tree = std::move(t);
         }
-        mirror_tree(q);
-        q->have_octree = true; q->validated = false;
-        int rc = set_setting(q, "octree_root_index", "OCTREE_ROOT_INDEX", setting_or(h, "octree_root_index", 0));
-        if (rc != VRC_OK) return rc;
+        VRC_TRY(set_setting(q, "octree_root_index", "OCTREE_ROOT_INDEX", setting_or(h, "octree_root_index", 0)));
     }
     for (vrc_caster *q : h->peers)
         if (q->owns_desc) { HIP_TRY(h, hipSetDevice(q->device)); HIP_TRY(h, hipStreamSynchronize(q->stream)); }
     HIP_TRY(h, hipSetDevice(h->device));
     return VRC_OK;
+}
+
+// The one way a handle gets a tree (after drop_trees): attach the complete tree, point the root setting at it, give it to the
+// peers.  adopted: the tree is another handle's too (vrc_assign_octree_from).
+int install_tree(vrc_caster *h, std::shared_ptr<vrc_tree> tree, uint64_t root_index, bool adopted = false) {
+    h->tree = std::move(tree);
+    h->owns_desc = !adopted;
+    VRC_TRY(set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)root_index));   // CLCaster.cpp:113
+    return fan_out_tree(h);
 }
 
 bool lookup_in_range(const uint32_t *lookup, size_t n, uint64_t n_attach) {
@@ -642,47 +650,36 @@ extern "C" {
 int vrc_assign_octree(vrc_caster *h, const uint64_t *descriptors, uint64_t n, uint64_t root_index) {
     if (!h || !descriptors || n == 0 || root_index >= n) return fail(h, VRC_ERR_INVALID_ARGUMENT, "assign_octree: bad argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    for (vrc_caster *q : h->peers) release_tree(q);
-    release_tree(h);                                               // a new tree never inherits the old one's materials
-    vrc_tree *t = new_tree(h);
+    drop_trees(h);
+    std::shared_ptr<vrc_tree> t = new_tree(h->device);
     HIP_TRY(h, hipMalloc((void **)&t->d_desc, n * sizeof(uint64_t)));
     HIP_TRY(h, hipMemcpy(t->d_desc, descriptors, n * sizeof(uint64_t), hipMemcpyHostToDevice));
     t->n_desc = n;
-    mirror_tree(h);
-    h->have_octree = true;
-    int rc = set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)root_index);   // CLCaster.cpp:113
-    if (rc != VRC_OK) return rc;
-    return fan_out_tree(h);
+    return install_tree(h, std::move(t), root_index);
 }
 
 // The tree another handle on the same GPU already holds, adopted instead of uploaded again: one descriptor array, one coarse
 // table, one set of empty boxes between the two (vrc_tree).  The arrays live until the last handle lets go of them.
 int vrc_assign_octree_from(vrc_caster *h, vrc_caster *src) {
     if (!h || !src || h == src) return fail(h, VRC_ERR_INVALID_ARGUMENT, "assign_octree_from: bad argument");
-    if (!src->tree || !src->have_octree) return fail(h, VRC_ERR_NOT_READY, "assign_octree_from: the source handle has no octree");
+    if (!src->tree) return fail(h, VRC_ERR_NOT_READY, "assign_octree_from: the source handle has no octree");
     if (src->device != h->device) return fail(h, VRC_ERR_INVALID_ARGUMENT, "assign_octree_from: the handles sit on different GPUs (%d, %d)", h->device, src->device);
     HIP_TRY(h, hipSetDevice(h->device));
     std::shared_ptr<vrc_tree> keep = src->tree;                    // (src may be a peer of h's own group)
-    for (vrc_caster *q : h->peers) release_tree(q);
-    release_tree(h);
-    h->tree = keep;
-    h->owns_desc = false;
-    mirror_tree(h);
-    h->have_octree = true;
-    const int rc = set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", setting_or(src, "octree_root_index", 0));
-    if (rc != VRC_OK) return rc;
-    return fan_out_tree(h);
+    const int64_t root = setting_or(src, "octree_root_index", 0);
+    drop_trees(h);
+    return install_tree(h, std::move(keep), (uint64_t)root, true);
 }
 
 int vrc_assign_octree_attachments(vrc_caster *h, const uint32_t *lookup, uint64_t n_lookup,
                                   const uint64_t *attachments, uint64_t n_attachments) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    if (!h->have_octree) return fail(h, VRC_ERR_NOT_READY, "assign_octree_attachments: assign the octree first");
+    if (!h->tree) return fail(h, VRC_ERR_NOT_READY, "assign_octree_attachments: assign the octree first");
     HIP_TRY(h, hipSetDevice(h->device));
     // the arguments are checked before anything is touched: a rejected call leaves every rank as it was
     const bool have = lookup && n_lookup && attachments && n_attachments;
     if (have) {
-        if (n_lookup != h->n_desc)
+        if (n_lookup != h->tree->n_desc)
             return fail(h, VRC_ERR_INVALID_ARGUMENT, "assign_octree_attachments: lookup must have one entry per descriptor");
         if (!lookup_in_range(lookup, (size_t)n_lookup, n_attachments))
             return fail(h, VRC_ERR_INVALID_ARGUMENT, "assign_octree_attachments: a lookup entry points past the attachment buffer");
@@ -693,10 +690,9 @@ int vrc_assign_octree_attachments(vrc_caster *h, const uint32_t *lookup, uint64_
     auto drop = [](vrc_caster *q) {
         vrc_tree *t = q->tree.get();
         if (t) {
-            std::lock_guard<std::mutex> lock(t->guard);            // (another holder's frame copies these pointers under the guard)
+            std::lock_guard<std::mutex> lock(t->guard);            // (another holder's frame reads these pointers under the guard)
             (void)hipSetDevice(t->device); release(t->d_attach_lookup); release(t->d_attach); t->n_attach = 0;
         }
-        mirror_tree(q);
         q->validated = false;
     };
     for (vrc_caster *q : h->peers) drop(q);
@@ -711,20 +707,18 @@ int vrc_assign_octree_attachments(vrc_caster *h, const uint32_t *lookup, uint64_
         HIP_TRY(h, hipMemcpy(t->d_attach, attachments, n_attachments * sizeof(uint64_t), hipMemcpyHostToDevice));
         t->n_attach = n_attachments;
     }
-    mirror_tree(h);
     if (h->peers.empty()) return VRC_OK;
     // ranks with their own copy of the descriptors: only the attachment buffers change
     for (vrc_caster *q : h->peers) {
         vrc_tree *tq = q->tree.get();
-        if (tq != t && h->d_attach_lookup && h->d_attach) {
+        if (tq && tq != t && t->d_attach_lookup && t->d_attach) {   // (no tree: the rank's copy failed in the fan-out)
             HIP_TRY(h, hipSetDevice(q->device));
-            HIP_TRY(h, hipMalloc((void **)&tq->d_attach_lookup, h->n_desc * sizeof(uint32_t)));
-            HIP_TRY(h, hipMalloc((void **)&tq->d_attach, h->n_attach * sizeof(uint64_t)));
-            HIP_TRY(h, hipMemcpyPeer(tq->d_attach_lookup, q->device, h->d_attach_lookup, h->device, h->n_desc * sizeof(uint32_t)));
-            HIP_TRY(h, hipMemcpyPeer(tq->d_attach, q->device, h->d_attach, h->device, h->n_attach * sizeof(uint64_t)));
-            tq->n_attach = h->n_attach;
+            HIP_TRY(h, hipMalloc((void **)&tq->d_attach_lookup, t->n_desc * sizeof(uint32_t)));
+            HIP_TRY(h, hipMalloc((void **)&tq->d_attach, t->n_attach * sizeof(uint64_t)));
+            HIP_TRY(h, hipMemcpyPeer(tq->d_attach_lookup, q->device, t->d_attach_lookup, h->device, t->n_desc * sizeof(uint32_t)));
+            HIP_TRY(h, hipMemcpyPeer(tq->d_attach, q->device, t->d_attach, h->device, t->n_attach * sizeof(uint64_t)));
+            tq->n_attach = t->n_attach;
         }
-        mirror_tree(q);
     }
     HIP_TRY(h, hipSetDevice(h->device));
     return VRC_OK;
@@ -773,14 +767,13 @@ int vrc_assign_octree_file(vrc_caster *h, const char *path, uint32_t *dim) {
                         fread(&flags, 4, 1, f) == 1 && fread(&root, 8, 1, f) == 1 && fread(&n, 8, 1, f) == 1 &&
                         fread(&na, 8, 1, f) == 1 && n > 0 && root < n && *dim >= 2 && (*dim & (*dim - 1)) == 0;
     if (!header) { fclose(f); return fail(h, VRC_ERR_INVALID_ARGUMENT, "assign_octree_file: '%s' is not a VRCSVO01 file", path); }
-    for (vrc_caster *q : h->peers) release_tree(q);
-    release_tree(h);
+    drop_trees(h);
     const size_t chunk = (size_t)setting_or(h, "upload_chunk_bytes", 64 << 20);
     void *stage[2] = {nullptr, nullptr};
     int rc = VRC_OK;
     if (chunk < 4096 || hipHostMalloc(&stage[0], chunk, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&stage[1], chunk, hipHostMallocDefault) != hipSuccess)
         rc = fail(h, VRC_ERR_OUT_OF_MEMORY, "assign_octree_file: no pinned staging memory");
-    vrc_tree *t = new_tree(h);
+    std::shared_ptr<vrc_tree> t = new_tree(h->device);
     if (rc == VRC_OK && hipMalloc((void **)&t->d_desc, n * sizeof(uint64_t)) != hipSuccess)
         rc = fail(h, VRC_ERR_OUT_OF_MEMORY, "assign_octree_file: %llu descriptors do not fit in device memory", (unsigned long long)n);
     if (rc == VRC_OK) rc = stream_to_device(h, f, t->d_desc, n * sizeof(uint64_t), stage, chunk, nullptr, 0);
@@ -795,13 +788,9 @@ int vrc_assign_octree_file(vrc_caster *h, const char *path, uint32_t *dim) {
     }
     fclose(f);
     for (int i = 0; i < 2; i++) if (stage[i]) (void)hipHostFree(stage[i]);
-    if (rc != VRC_OK) { release_tree(h); return rc; }
+    if (rc != VRC_OK) return rc;                                   // (the half-filled tree goes with t)
     t->n_desc = n; t->n_attach = (flags & 1u) ? std::max<uint64_t>(na, 1) : 0;
-    mirror_tree(h);
-    h->have_octree = true;
-    rc = set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)root);   // CLCaster.cpp:113
-    if (rc != VRC_OK) return rc;
-    return fan_out_tree(h);
+    return install_tree(h, std::move(t), root);
 }
 
 int vrc_build_shell_terrain(vrc_caster *h, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
@@ -811,10 +800,7 @@ int vrc_build_shell_terrain(vrc_caster *h, uint32_t depth, uint64_t seed, int32_
         return fail(h, VRC_ERR_INVALID_ARGUMENT, "build_shell_terrain: need 3 <= depth <= 16, thickness >= 0, octave_floor >= 0");
     HIP_TRY(h, hipSetDevice(h->device));
     const bool count_only = (flags & VRC_BUILD_COUNT_ONLY) != 0;
-    if (!count_only) {
-        for (vrc_caster *q : h->peers) release_tree(q);
-        release_tree(h);
-    }
+    if (!count_only) drop_trees(h);
     uint64_t *d = nullptr;
     vrc_build_info bi;
     std::string err;
@@ -823,11 +809,7 @@ int vrc_build_shell_terrain(vrc_caster *h, uint32_t depth, uint64_t seed, int32_
     if (info) *info = bi;
     if (rc != VRC_OK) return fail(h, rc, "build_shell_terrain: %s", err.c_str());
     if (count_only) return VRC_OK;
-    { vrc_tree *t = new_tree(h); t->d_desc = d; t->n_desc = bi.n_descriptors; mirror_tree(h); }
-    h->have_octree = true;
-    const int rs = set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)bi.root_index);
-    if (rs != VRC_OK) return rs;
-    return fan_out_tree(h);
+    return install_tree(h, new_tree(h->device, d, bi.n_descriptors), bi.root_index);
 }
 
 int vrc_build_heightfield(vrc_caster *h, uint32_t depth, const uint16_t *hi, const uint16_t *lo, uint32_t flags,
@@ -840,10 +822,7 @@ int vrc_build_heightfield(vrc_caster *h, uint32_t depth, const uint16_t *hi, con
             return fail(h, VRC_ERR_INVALID_ARGUMENT, "build_heightfield: column %zu needs lo <= hi < dim", i);
     HIP_TRY(h, hipSetDevice(h->device));
     const bool count_only = (flags & VRC_BUILD_COUNT_ONLY) != 0;
-    if (!count_only) {
-        for (vrc_caster *q : h->peers) release_tree(q);
-        release_tree(h);
-    }
+    if (!count_only) drop_trees(h);
     uint64_t *d = nullptr;
     vrc_build_info bi;
     std::string err;
@@ -851,11 +830,7 @@ int vrc_build_heightfield(vrc_caster *h, uint32_t depth, const uint16_t *hi, con
     if (info) *info = bi;
     if (rc != VRC_OK) return fail(h, rc, "build_heightfield: %s", err.c_str());
     if (count_only) return VRC_OK;
-    { vrc_tree *t = new_tree(h); t->d_desc = d; t->n_desc = bi.n_descriptors; mirror_tree(h); }
-    h->have_octree = true;
-    const int rs = set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)bi.root_index);
-    if (rs != VRC_OK) return rs;
-    return fan_out_tree(h);
+    return install_tree(h, new_tree(h->device, d, bi.n_descriptors), bi.root_index);
 }
 
 int vrc_build_dense_grid(vrc_caster *h, uint32_t depth, const int8_t *grid, uint32_t flags, uint64_t validate_samples,
@@ -867,10 +842,7 @@ int vrc_build_dense_grid(vrc_caster *h, uint32_t depth, const int8_t *grid, uint
         return fail(h, VRC_ERR_INVALID_ARGUMENT, "build_dense_grid: no grid given and no %d^3 map assigned (vrc_assign_map) to build from", dim);
     HIP_TRY(h, hipSetDevice(h->device));
     const bool count_only = (flags & VRC_BUILD_COUNT_ONLY) != 0;
-    if (!count_only) {
-        for (vrc_caster *q : h->peers) release_tree(q);
-        release_tree(h);
-    }
+    if (!count_only) drop_trees(h);
     uint64_t *d = nullptr;
     vrc_build_info bi;
     std::string err;
@@ -881,40 +853,32 @@ int vrc_build_dense_grid(vrc_caster *h, uint32_t depth, const int8_t *grid, uint
     if (info) *info = bi;
     if (rc != VRC_OK) return fail(h, rc, "build_dense_grid: %s", err.c_str());
     if (count_only) return VRC_OK;
-    {
-        vrc_tree *t = new_tree(h);
-        t->d_desc = d; t->n_desc = bi.n_descriptors;
-        t->d_attach_lookup = lookup; t->d_attach = attach; t->n_attach = n_attach;
-        mirror_tree(h);
-    }
-    h->have_octree = true;
-    const int rs = set_setting(h, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)bi.root_index);
-    if (rs != VRC_OK) return rs;
-    return fan_out_tree(h);
+    std::shared_ptr<vrc_tree> t = new_tree(h->device, d, bi.n_descriptors);
+    t->d_attach_lookup = lookup; t->d_attach = attach; t->n_attach = n_attach;
+    return install_tree(h, std::move(t), bi.root_index);
 }
 
 int vrc_read_descriptors(vrc_caster *h, uint64_t first, uint64_t count, uint64_t *out) {
     if (!h || !out) return VRC_ERR_INVALID_ARGUMENT;
-    if (!h->have_octree) return fail(h, VRC_ERR_NOT_READY, "read_descriptors: no octree assigned");
-    if (first > h->n_desc || count > h->n_desc - first) return fail(h, VRC_ERR_INVALID_ARGUMENT, "read_descriptors: range past the array");
+    if (!h->tree) return fail(h, VRC_ERR_NOT_READY, "read_descriptors: no octree assigned");
+    if (first > h->tree->n_desc || count > h->tree->n_desc - first) return fail(h, VRC_ERR_INVALID_ARGUMENT, "read_descriptors: range past the array");
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpy(out, h->d_desc + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(out, h->tree->d_desc + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VRC_OK;
 }
 
 int vrc_octree_size(vrc_caster *h, uint64_t *n_descriptors, uint64_t *root_index) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    if (!h->have_octree) return fail(h, VRC_ERR_NOT_READY, "octree_size: no octree assigned");
-    if (n_descriptors) *n_descriptors = h->n_desc;
+    if (!h->tree) return fail(h, VRC_ERR_NOT_READY, "octree_size: no octree assigned");
+    if (n_descriptors) *n_descriptors = h->tree->n_desc;
     if (root_index) *root_index = (uint64_t)setting_or(h, "octree_root_index", 0);
     return VRC_OK;
 }
 
 int vrc_release_octree(vrc_caster *h) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    if (!h->d_desc) return fail(h, VRC_ERR_NOT_FOUND, "release_octree: no octree assigned");
-    for (vrc_caster *q : h->peers) release_tree(q);               // ranks sharing rank 0's arrays must let go first
-    release_tree(h);
+    if (!h->tree) return fail(h, VRC_ERR_NOT_FOUND, "release_octree: no octree assigned");
+    drop_trees(h);
     release_query_staging(h);
     return VRC_OK;
 }
@@ -922,16 +886,14 @@ int vrc_release_octree(vrc_caster *h) {
 int vrc_create_viewport(vrc_caster *h, int32_t width, int32_t height, float v_fov, float h_fov) {
     (void)v_fov; (void)h_fov;              // ignored by the reference too (CLCaster.cpp:233-275)
     if (!h || width <= 0 || height <= 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "create_viewport: bad size");
-    const int rc = install_viewport(h, width, height, nullptr);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(install_viewport(h, width, height, nullptr));
     FOR_PEERS(h, vrc_create_viewport(q, width, height, v_fov, h_fov));
     return VRC_OK;
 }
 
 int vrc_create_viewport_table(vrc_caster *h, int32_t width, int32_t height, const float *table) {
     if (!h || !table || width <= 0 || height <= 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "create_viewport_table: bad argument");
-    const int rc = install_viewport(h, width, height, table);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(install_viewport(h, width, height, table));
     FOR_PEERS(h, vrc_create_viewport_table(q, width, height, table));
     return VRC_OK;
 }
@@ -939,7 +901,7 @@ int vrc_create_viewport_table(vrc_caster *h, int32_t width, int32_t height, cons
 int vrc_release_viewport(vrc_caster *h) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
     if (!h->d_viewport) return fail(h, VRC_ERR_NOT_FOUND, "release_viewport: no viewport");
-    release(h->d_viewport); release(h->d_image); release(h->d_hits); release(h->d_rgba8); release(h->d_jump_cache); release(h->d_jump_slots); h->jump_slot_count = 0;
+    release_viewport_buffers(h);
     release_query_staging(h);
     h->width = h->height = h->buffer_rows = 0; h->validated = false;
     FOR_PEERS(h, vrc_release_viewport(q));
@@ -992,8 +954,7 @@ int vrc_assign_lights(vrc_caster *h, const float *packed, const int32_t *light_c
 
 int vrc_setting_add(vrc_caster *h, const char *name, const char *define, int64_t value) {
     if (!h || !name) return VRC_ERR_INVALID_ARGUMENT;
-    const int rc = set_setting(h, name, define, value);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(set_setting(h, name, define, value));
     FOR_PEERS(h, vrc_setting_add(q, name, define, value));
     return VRC_OK;
 }
@@ -1042,7 +1003,7 @@ int vrc_validate(vrc_caster *h) {
     if (!h->d_viewport || !h->d_image) return fail(h, VRC_ERR_NOT_READY, "validate: viewport not created");
     if (!h->lights) return fail(h, VRC_ERR_NOT_READY, "validate: lights not assigned");
     if (!h->d_atlas) return fail(h, VRC_ERR_NOT_READY, "validate: texture atlas not created");
-    if (!h->have_octree) return fail(h, VRC_ERR_NOT_READY, "validate: octree not assigned");
+    if (!h->tree) return fail(h, VRC_ERR_NOT_READY, "validate: octree not assigned");
     if (find_setting(h, "octree_dimensions") < 0) return fail(h, VRC_ERR_NOT_READY, "validate: setting octree_dimensions missing");
     if (find_setting(h, "using_octree") < 0) return fail(h, VRC_ERR_NOT_READY, "validate: setting using_octree missing");
     const int64_t dim = setting_or(h, "octree_dimensions", 0);
@@ -1050,7 +1011,7 @@ int vrc_validate(vrc_caster *h) {
     if (n < 1) return fail(h, VRC_ERR_INVALID_ARGUMENT, "validate: octree_dimensions must be a power of two >= 2");
     if (n > vrc::kMaxLevels) return fail(h, VRC_ERR_LIMIT, "validate: octree deeper than %d levels", vrc::kMaxLevels);
     const int64_t root = setting_or(h, "octree_root_index", 0);
-    if (root < 0 || (uint64_t)root >= h->n_desc) return fail(h, VRC_ERR_INVALID_ARGUMENT, "validate: octree_root_index out of range");
+    if (root < 0 || (uint64_t)root >= h->tree->n_desc) return fail(h, VRC_ERR_INVALID_ARGUMENT, "validate: octree_root_index out of range");
     if (setting_or(h, "using_octree", 0) != 0) {
         if (!h->d_map) return fail(h, VRC_ERR_NOT_READY, "validate: dense map not assigned (using_octree != 0 selects the array branch)");
     }
@@ -1068,8 +1029,7 @@ int vrc_validate(vrc_caster *h) {
 
 int vrc_prepare(vrc_caster *h) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    const int rc = prepare_one(h);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(prepare_one(h));
     FOR_PEERS(h, prepare_one(q));
     if (!h->peers.empty()) HIP_TRY(h, hipSetDevice(h->device));
     return VRC_OK;
@@ -1078,6 +1038,29 @@ int vrc_prepare(vrc_caster *h) {
 }  // extern "C"
 
 namespace {
+
+// Build-or-remember-failure of one derived structure.  `have`: it exists; it is kept when it was built for `want`.  Else drop()
+// frees it and build() makes it anew -- unless just this (`want_failed`) failed before and the host has not asked again
+// (retry_derived).  A failure leaves no structure behind, only its key and the reason: what is missing, then the runtime's error text.
+std::string missing(const TableKey &k) { return "no coarse table (level " + std::to_string(k.log2) + ")"; }
+std::string missing(const BoxKey &) { return "no empty boxes"; }
+template <class Key, class Drop, class Build>
+void rebuild(Derived<Key> &d, bool have, const Key &want, const Key &want_failed, Drop drop, Build build) {
+    if (have && d.built == want) return;
+    drop();
+    d.built = Key{};
+    if (d.gave_up && d.failed == want_failed) return;
+    const hipError_t e = build();
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        drop();
+        d.gave_up = true; d.failed = want_failed;
+        d.note = missing(want_failed) + ": " + hipGetErrorString(e) + "; ";
+    } else {
+        d.built = want;
+        d.gave_up = false; d.note.clear();
+    }
+}
 
 // The structures the SVO kernels derive from a tree, for these settings: built when missing or built for another (root, depth,
 // level); the kernel parameters get the pointers.  The caller holds t->guard.  Both structures are optional accelerations: when
@@ -1093,30 +1076,19 @@ void derive_from_tree(vrc_caster *h, vrc_tree *t, int log2_dim, uint64_t root_in
         while (lc >= 1 && ((uint64_t)sizeof(uint64_t) << (3 * lc)) > 16 * sizeof(uint64_t) * t->n_desc && ((uint64_t)sizeof(uint64_t) << (3 * lc)) > (1u << 20)) lc--;
     }
     lc = std::min<int64_t>(lc, std::min(log2_dim - 2, 10));
+    const TableKey at{(int)lc, root_index, log2_dim};
     if (lc >= 1 && t->n_desc < (1ULL << 43)) {
-        if (!t->d_coarse || t->coarse_log2 != (int)lc || t->coarse_root != root_index || t->coarse_depth != log2_dim) {
-            release(t->d_coarse);
-            release_boxes(t);                                      // (the boxes' parallel word belongs to the table's cells)
-            t->coarse_log2 = 0;
-            const bool failed_before = t->coarse_gave_up && t->coarse_fail_log2 == (int)lc && t->coarse_fail_root == root_index && t->coarse_fail_depth == log2_dim;
-            if (!failed_before) {
-                hipError_t e = hipMalloc((void **)&t->d_coarse, sizeof(uint64_t) << (3 * lc));
-                if (e == hipSuccess) e = vrc::launch_coarse_build(t->d_desc, root_index, log2_dim, (int)lc, t->d_coarse, h->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(h->stream);          // other handles read it from their own streams
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    release(t->d_coarse);
-                    t->coarse_gave_up = true; t->coarse_fail_log2 = (int)lc; t->coarse_fail_root = root_index; t->coarse_fail_depth = log2_dim;
-                    t->coarse_note = std::string("no coarse table (level ") + std::to_string(lc) + "): " + hipGetErrorString(e) + "; ";
-                } else {
-                    t->coarse_log2 = (int)lc; t->coarse_root = root_index; t->coarse_depth = log2_dim;
-                    t->coarse_gave_up = false; t->coarse_note.clear();
-                }
-            }
-        }
+        rebuild(t->coarse, t->d_coarse != nullptr, at, at,
+                [&] { release(t->d_coarse); release_boxes(t); },   // (the boxes' parallel word belongs to the table's cells)
+                [&] {
+                    hipError_t e = hipMalloc((void **)&t->d_coarse, sizeof(uint64_t) << (3 * lc));
+                    if (e == hipSuccess) e = vrc::launch_coarse_build(t->d_desc, root_index, log2_dim, (int)lc, t->d_coarse, h->stream);
+                    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);          // other handles read it from their own streams
+                    return e;
+                });
         if (t->d_coarse) { p.coarse = t->d_coarse; p.coarse_log2 = (int32_t)lc; }
     } else if (t->d_coarse) {
-        release(t->d_coarse); t->coarse_log2 = 0;             // the setting went to "none": the table goes too
+        release(t->d_coarse); t->coarse.built = TableKey{};   // the setting went to "none": the table goes too
         release_boxes(t);
     }
     // the empty boxes (empty_boxes.hip; setting empty_boxes: -1 = when the tree is small enough for them, 0 = never, 1 = always):
@@ -1140,58 +1112,49 @@ void derive_from_tree(vrc_caster *h, vrc_tree *t, int log2_dim, uint64_t root_in
     if (box_mode) {
         const int64_t want_levels = box_mode == 2 ? std::max<int64_t>(0, setting_or(h, "empty_box_levels", 0)) : 0;
         const int64_t want_records = box_mode == 2 ? std::max<int64_t>(0, setting_or(h, "empty_box_records", 0)) : 0;
-        if (!t->d_boxes || t->box_mode != box_mode || t->box_levels_asked != want_levels || t->box_records_asked != want_records || t->box_log2 != (int)lc || t->box_root != root_index || t->box_depth != log2_dim) {
-            release_boxes(t);
-            const bool failed_before = t->boxes_gave_up && t->box_fail_log2 == (int)lc && t->box_fail_root == root_index && t->box_fail_depth == log2_dim && t->box_fail_mode == box_mode;
-            if (!failed_before) {
-                uint64_t *pos_tmp = nullptr;
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                float ms = 0.f;
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-                hipError_t e = hipMalloc((void **)&t->d_box_aux, sizeof(uint32_t) << (3 * lc));
-                if (e == hipSuccess) e = hipEventCreate(&e0);
-                if (e == hipSuccess) e = hipEventCreate(&e1);
-                if (e == hipSuccess) e = hipEventRecord(e0, h->stream);
-                if (box_mode == 1) {
-                    // (an optional structure must not be what makes the next allocation fail: at most half of what is free right now)
-                    if (e == hipSuccess && want_boxes < 0 && t->n_desc > (1ULL << 28) && 40ULL * t->n_desc > free_b / 2) e = hipErrorOutOfMemory;
-                    if (e == hipSuccess) e = hipMalloc((void **)&t->d_boxes, sizeof(uint32_t) * 8 * t->n_desc);
-                    if (e == hipSuccess) e = hipMalloc((void **)&pos_tmp, sizeof(uint64_t) * t->n_desc);
-                    if (e == hipSuccess) e = vrc::launch_box_build(t->d_desc, t->n_desc, root_index, log2_dim, (int)lc, pos_tmp, t->d_boxes, t->d_box_aux, h->stream);
-                    if (e == hipSuccess) { t->box_records = t->n_desc; t->box_levels = log2_dim; }
-                } else {
-                    uint64_t budget = (uint64_t)want_records;
-                    // (measured on the depth-16 terrain, 5.7 G descriptors: 200 M records 4.59 ms, 400 M 4.47, 1.5 G 5.04 -- beyond ~15 GB the
-                    // words themselves become TLB misses; without boxes 4.73)
-                    if (!budget) budget = std::min<uint64_t>(400000000ULL, (uint64_t)(free_b / 4) / 52);
-                    budget = std::min<uint64_t>(budget, 0xffffff00ULL);
-                    vrc::BoxUpper u;
-                    if (e == hipSuccess) e = vrc::launch_box_build_upper(t->d_desc, root_index, log2_dim, (int)lc, std::max<uint64_t>(budget, 9), (int)want_levels, &u, t->d_box_aux, h->stream);
-                    if (e == hipSuccess) {
-                        t->d_boxes = u.boxes; t->d_box_child = u.child; t->d_box_desc = u.desc; t->d_box_pos = u.pos;
-                        t->box_records = u.count; t->box_levels = u.levels;
+        // (a failure is remembered for the level, root, depth and form alone -- not for the levels and records asked)
+        rebuild(t->boxes, t->d_boxes != nullptr, BoxKey{at, box_mode, want_levels, want_records}, BoxKey{at, box_mode},
+                [&] { release_boxes(t); },
+                [&] {
+                    uint64_t *pos_tmp = nullptr;
+                    hipEvent_t e0 = nullptr, e1 = nullptr;
+                    float ms = 0.f;
+                    size_t free_b = 0, total_b = 0;
+                    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+                    hipError_t e = hipMalloc((void **)&t->d_box_aux, sizeof(uint32_t) << (3 * lc));
+                    if (e == hipSuccess) e = hipEventCreate(&e0);
+                    if (e == hipSuccess) e = hipEventCreate(&e1);
+                    if (e == hipSuccess) e = hipEventRecord(e0, h->stream);
+                    if (box_mode == 1) {
+                        // (an optional structure must not be what makes the next allocation fail: at most half of what is free right now)
+                        if (e == hipSuccess && want_boxes < 0 && t->n_desc > (1ULL << 28) && 40ULL * t->n_desc > free_b / 2) e = hipErrorOutOfMemory;
+                        if (e == hipSuccess) e = hipMalloc((void **)&t->d_boxes, sizeof(uint32_t) * 8 * t->n_desc);
+                        if (e == hipSuccess) e = hipMalloc((void **)&pos_tmp, sizeof(uint64_t) * t->n_desc);
+                        if (e == hipSuccess) e = vrc::launch_box_build(t->d_desc, t->n_desc, root_index, log2_dim, (int)lc, pos_tmp, t->d_boxes, t->d_box_aux, h->stream);
+                        if (e == hipSuccess) { t->box_records = t->n_desc; t->box_levels = log2_dim; }
+                    } else {
+                        uint64_t budget = (uint64_t)want_records;
+                        // (measured on the depth-16 terrain, 5.7 G descriptors: 200 M records 4.59 ms, 400 M 4.47, 1.5 G 5.04 -- beyond ~15 GB the
+                        // words themselves become TLB misses; without boxes 4.73)
+                        if (!budget) budget = std::min<uint64_t>(400000000ULL, (uint64_t)(free_b / 4) / 52);
+                        budget = std::min<uint64_t>(budget, 0xffffff00ULL);
+                        vrc::BoxUpper u;
+                        if (e == hipSuccess) e = vrc::launch_box_build_upper(t->d_desc, root_index, log2_dim, (int)lc, std::max<uint64_t>(budget, 9), (int)want_levels, &u, t->d_box_aux, h->stream);
+                        if (e == hipSuccess) {
+                            t->d_boxes = u.boxes; t->d_box_child = u.child; t->d_box_desc = u.desc; t->d_box_pos = u.pos;
+                            t->box_records = u.count; t->box_levels = u.levels;
+                        }
                     }
-                }
-                if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-                if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
-                if (e == hipSuccess && vrc::box_queries_cut(&t->box_queries_cut) != hipSuccess) { (void)hipGetLastError(); t->box_queries_cut = 0; }
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-                if (pos_tmp) (void)hipFree(pos_tmp);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    release_boxes(t);
-                    t->boxes_gave_up = true; t->box_fail_log2 = (int)lc; t->box_fail_root = root_index; t->box_fail_depth = log2_dim; t->box_fail_mode = box_mode;
-                    t->box_note = std::string("no empty boxes: ") + hipGetErrorString(e) + "; ";
-                } else {
-                    t->box_build_seconds = ms * 1e-3;
-                    t->box_log2 = (int)lc; t->box_root = root_index; t->box_depth = log2_dim; t->box_mode = box_mode; t->box_levels_asked = want_levels; t->box_records_asked = want_records;
-                    t->boxes_gave_up = false; t->box_note.clear();
-                }
-            }
-        }
+                    if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
+                    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+                    if (e == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+                    if (e == hipSuccess && vrc::box_queries_cut(&t->box_queries_cut) != hipSuccess) { (void)hipGetLastError(); t->box_queries_cut = 0; }
+                    if (e0) (void)hipEventDestroy(e0);
+                    if (e1) (void)hipEventDestroy(e1);
+                    if (pos_tmp) (void)hipFree(pos_tmp);
+                    if (e == hipSuccess) t->box_build_seconds = ms * 1e-3;
+                    return e;
+                });
         if (t->d_boxes) { p.boxes = t->d_boxes; p.box_aux = t->d_box_aux; p.box_child = t->d_box_child; p.box_levels = t->box_levels; }
     }
     // (a handle that switches the boxes off keeps them: they belong to the tree, go with it, and a host that toggles the setting
@@ -1200,7 +1163,7 @@ void derive_from_tree(vrc_caster *h, vrc_tree *t, int log2_dim, uint64_t root_in
 
 // vrc_prepare for one rank: the derived structures for the settings as they stand
 int prepare_one(vrc_caster *h) {
-    if (!h->have_octree || !h->tree) return fail(h, VRC_ERR_NOT_READY, "prepare: octree not assigned");
+    if (!h->tree) return fail(h, VRC_ERR_NOT_READY, "prepare: octree not assigned");
     const int n = log2_exact(setting_or(h, "octree_dimensions", 0));
     if (n < 1 || n > vrc::kMaxLevels) return fail(h, VRC_ERR_NOT_READY, "prepare: setting octree_dimensions missing or not a power of two in [2, 2^%d]", vrc::kMaxLevels);
     const int64_t root = setting_or(h, "octree_root_index", 0);
@@ -1220,11 +1183,10 @@ int compute_async_one(vrc_caster *h) {
     // The tree's guard is held from here until the kernel is ENQUEUED: another holder of the tree (another host thread, other
     // settings, new materials) that replaces one of its arrays frees the old one with hipFree, which waits for the kernels already
     // enqueued -- never for a frame that has copied the pointers and not launched yet (advisor finding, round 5).
+    // (read from the tree itself, under the guard: a handle that shares it may have given it new materials since the last frame)
+    vrc_tree *t = h->tree.get();
     std::unique_lock<std::mutex> tree_lock;
-    if (h->tree) {
-        tree_lock = std::unique_lock<std::mutex>(h->tree->guard);
-        mirror_tree(h);                    // (a handle that shares the tree may have given it new materials since the last frame)
-    }
+    if (t) tree_lock = std::unique_lock<std::mutex>(t->guard);
 
     // settings stay live after validate() (CLCaster::overwrite_setting needs no recompile, CLCaster.cpp:1087-1109), so
     // the structural ones are checked again here: a bad value is an error return, never a device fault
@@ -1237,7 +1199,7 @@ int compute_async_one(vrc_caster *h) {
     if (p.log2_dim < 1 || p.log2_dim > vrc::kMaxLevels)
         return fail(h, VRC_ERR_INVALID_ARGUMENT, "compute: octree_dimensions must be a power of two in [2, 2^%d]", vrc::kMaxLevels);
     const int64_t root = setting_or(h, "octree_root_index", 0);
-    if (!h->d_desc || root < 0 || (uint64_t)root >= h->n_desc) return fail(h, VRC_ERR_INVALID_ARGUMENT, "compute: octree_root_index out of range");
+    if (!t || root < 0 || (uint64_t)root >= t->n_desc) return fail(h, VRC_ERR_INVALID_ARGUMENT, "compute: octree_root_index out of range");
     if (!svo && !h->d_map) return fail(h, VRC_ERR_NOT_READY, "compute: dense map not assigned (using_octree != 0 selects the array branch)");
     if (!h->d_viewport || !h->d_image || !h->d_atlas) return fail(h, VRC_ERR_NOT_READY, "compute: viewport or atlas released since validate()");
     p.stepping_mode = (int32_t)setting_or(h, "stepping_mode", 0);
@@ -1248,17 +1210,15 @@ int compute_async_one(vrc_caster *h) {
     else { p.map_dim[0] = h->map_dim[0]; p.map_dim[1] = h->map_dim[1]; p.map_dim[2] = h->map_dim[2]; }
     p.width = h->width; p.height = h->height;
     if (setting_or(h, "hit_records", 1) != 0) {
-        const int rc = ensure_hits(h);
-        if (rc != VRC_OK) return rc;
+        VRC_TRY(ensure_hits(h));
         p.hits = h->d_hits;
     }
     h->last_frame_wrote_hits = p.hits != nullptr;
     p.viewport = h->d_viewport; p.image = h->d_image;
     p.atlas = h->d_atlas; p.atlas_w = h->atlas_w; p.atlas_h = h->atlas_h;
     p.tiles_x = h->atlas_w / h->tile_w; p.tiles_y = h->atlas_h / h->tile_h;
-    p.descriptors = h->d_desc;
-    p.attach_lookup = (h->d_attach_lookup && h->d_attach) ? h->d_attach_lookup : nullptr;
-    p.attachments = p.attach_lookup ? h->d_attach : nullptr;
+    p.descriptors = t->d_desc;
+    bind_attachments(t, p);
     p.root_index = (uint64_t)root;
     // live buffers are re-read every frame (CL_MEM_USE_HOST_PTR semantics)
     for (int a = 0; a < 3; a++) p.cam_pos[a] = h->cam_pos[a];
@@ -1332,7 +1292,7 @@ int compute_async_one(vrc_caster *h) {
     p.counters = h->d_partials;
     // What the kernels derive from the tree (the dense table of its top, the empty boxes) lives WITH the tree and is built by
     // vrc_prepare / vrc_validate; a frame that finds it missing or built for other settings builds it here (under the guard).
-    if (svo) derive_from_tree(h, h->tree.get(), p.log2_dim, p.root_index, p.stepping_mode, p);
+    if (svo) derive_from_tree(h, t, p.log2_dim, p.root_index, p.stepping_mode, p);
     // exact closed-form jumps: on from depth 12; the threshold depends on where the Euclid tables live (LDS when stack + tables
     // fit at full occupancy: depth 12)
     p.jump_tables_lds = (int32_t)std::min<int64_t>(2, std::max<int64_t>(0, setting_or(h, "jump_tables_lds", 2)));
@@ -1346,8 +1306,7 @@ int compute_async_one(vrc_caster *h) {
     p.safe_steps = (int32_t)std::min<int64_t>(256, std::max<int64_t>(2, setting_or(h, "safe_steps",
                                     p.jump_min_run < vrc::kJumpOff ? vrc::kDefaultSafeStepsJump : vrc::kDefaultSafeSteps)));
     if (svo && p.stepping_mode == 0 && p.jump_min_run < vrc::kJumpOff && !tables_in_lds) {
-        const int rc = ensure_jump_cache(h, nblocks);
-        if (rc != VRC_OK) return rc;
+        VRC_TRY(ensure_jump_cache(h, nblocks));
         p.jump_cache = h->d_jump_cache; p.jump_slots = h->d_jump_slots; p.jump_slot_count = h->jump_slot_count;
     }
     h->last_frame_boxes = p.boxes != nullptr;
@@ -1399,8 +1358,7 @@ extern "C" {
 
 int vrc_compute_async(vrc_caster *h) {
     if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    const int rc = compute_async_one(h);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(compute_async_one(h));
     FOR_PEERS(h, compute_async_one(q));
     if (!h->peers.empty()) HIP_TRY(h, hipSetDevice(h->device));
     return VRC_OK;
@@ -1495,19 +1453,20 @@ int vrc_empty_boxes_check(vrc_caster *h, uint64_t samples, uint64_t seed, uint64
     uint64_t *pos = nullptr; unsigned long long *res = nullptr;
     hipError_t e = hipMalloc((void **)&res, 2 * sizeof(unsigned long long));
     unsigned long long out[2] = {0, 0}, cells[2] = {0, 0};
-    if (t->d_boxes && t->box_mode == 2) {                      // the records of the upper levels (their descriptors and positions were kept)
-        if (e == hipSuccess) e = vrc::launch_box_check(t->d_desc, t->box_records, t->box_root, t->box_depth, t->d_box_pos, t->d_box_desc, t->d_boxes, samples, seed, res, h->stream);
+    const TableKey &at = t->boxes.built.at;
+    if (t->d_boxes && t->boxes.built.mode == 2) {              // the records of the upper levels (their descriptors and positions were kept)
+        if (e == hipSuccess) e = vrc::launch_box_check(t->d_desc, t->box_records, at.root, at.depth, t->d_box_pos, t->d_box_desc, t->d_boxes, samples, seed, res, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e == hipSuccess) e = hipMemcpy(out, res, sizeof(out), hipMemcpyDeviceToHost);
     } else if (t->d_boxes) {                                   // the words per (descriptor, child)
         if (e == hipSuccess) e = hipMalloc((void **)&pos, sizeof(uint64_t) * t->n_desc);
-        if (e == hipSuccess) e = vrc::launch_box_positions(t->d_desc, t->n_desc, t->box_root, t->box_depth, pos, h->stream);
-        if (e == hipSuccess) e = vrc::launch_box_check(t->d_desc, t->n_desc, t->box_root, t->box_depth, pos, nullptr, t->d_boxes, samples, seed, res, h->stream);
+        if (e == hipSuccess) e = vrc::launch_box_positions(t->d_desc, t->n_desc, at.root, at.depth, pos, h->stream);
+        if (e == hipSuccess) e = vrc::launch_box_check(t->d_desc, t->n_desc, at.root, at.depth, pos, nullptr, t->d_boxes, samples, seed, res, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e == hipSuccess) e = hipMemcpy(out, res, sizeof(out), hipMemcpyDeviceToHost);
     }
     // the words of the table's cells (the coarse space)
-    if (e == hipSuccess) e = vrc::launch_box_check_cells(t->d_desc, t->box_root, t->box_depth, t->box_log2, t->d_box_aux, samples, seed + 1, res, h->stream);
+    if (e == hipSuccess) e = vrc::launch_box_check_cells(t->d_desc, at.root, at.depth, at.log2, t->d_box_aux, samples, seed + 1, res, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = hipMemcpy(cells, res, sizeof(cells), hipMemcpyDeviceToHost);
     out[0] += cells[0]; out[1] += cells[1];
@@ -1527,7 +1486,7 @@ int vrc_read_empty_boxes(vrc_caster *h, uint64_t first_descriptor, uint64_t coun
     if (!t) return fail(h, VRC_ERR_NOT_READY, "read_empty_boxes: no octree");
     std::lock_guard<std::mutex> lock(t->guard);
     if (!t->d_boxes) return fail(h, VRC_ERR_NOT_READY, "read_empty_boxes: no boxes (setting empty_boxes, or neither vrc_prepare nor a frame has run yet)");
-    if (t->box_mode != 1) return fail(h, VRC_ERR_NOT_READY, "read_empty_boxes: this tree has box records for its upper levels only (they are not indexed by descriptor)");
+    if (t->boxes.built.mode != 1) return fail(h, VRC_ERR_NOT_READY, "read_empty_boxes: this tree has box records for its upper levels only (they are not indexed by descriptor)");
     if (first_descriptor > t->n_desc || count > t->n_desc - first_descriptor) return fail(h, VRC_ERR_INVALID_ARGUMENT, "read_empty_boxes: range past the array");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpy(out, t->d_boxes + 8 * first_descriptor, sizeof(uint32_t) * 8 * count, hipMemcpyDeviceToHost));
@@ -1543,19 +1502,20 @@ int vrc_memory_usage2(vrc_caster *h, int32_t rank, vrc_memory2 *out) {
     const size_t npix = q->d_viewport ? (size_t)q->width * (size_t)std::max(q->buffer_rows, 1) : 0;
     m.device = q->device; m.rows = q->buffer_rows;
     m.viewport_bytes = 16 * npix; m.image_bytes = 16 * npix; m.hit_bytes = q->d_hits ? 32 * npix : 0;
-    m.octree_bytes = q->d_desc ? q->n_desc * 8 + (q->d_attach_lookup ? q->n_desc * 4 + std::max<uint64_t>(q->n_attach, 1) * 8 : 0) : 0;
     m.octree_shared = q->owns_desc ? 0 : 1;
     m.peer_access = q->peer_access;
     if (const vrc_tree *t = q->tree.get()) {
+        m.octree_bytes = t->n_desc * 8 + (t->d_attach_lookup ? t->n_desc * 4 + std::max<uint64_t>(t->n_attach, 1) * 8 : 0);
         m.tree_holders = (int32_t)q->tree.use_count();
-        m.coarse_log2 = t->d_coarse ? t->coarse_log2 : 0;
-        m.coarse_bytes = t->d_coarse ? (uint64_t)sizeof(uint64_t) << (3 * t->coarse_log2) : 0;
+        m.coarse_log2 = t->d_coarse ? t->coarse.built.log2 : 0;
+        m.coarse_bytes = t->d_coarse ? (uint64_t)sizeof(uint64_t) << (3 * t->coarse.built.log2) : 0;
         m.empty_boxes = q->last_frame_boxes ? 1 : 0;
-        m.box_bytes = (t->d_boxes ? (uint64_t)t->box_records * (32 + (t->box_mode == 2 ? 20 : 0)) : 0) + (t->d_box_aux ? (uint64_t)sizeof(uint32_t) << (3 * t->box_log2) : 0);
+        m.box_bytes = (t->d_boxes ? (uint64_t)t->box_records * (32 + (t->boxes.built.mode == 2 ? 20 : 0)) : 0) +
+                      (t->d_box_aux ? (uint64_t)sizeof(uint32_t) << (3 * t->boxes.built.at.log2) : 0);
         m.box_records = t->d_boxes ? t->box_records : 0;
         m.box_levels = t->d_boxes ? t->box_levels : 0;
         m.box_build_seconds = t->box_build_seconds;
-        snprintf(m.note, sizeof(m.note), "%s%s", t->coarse_note.c_str(), t->box_note.c_str());
+        snprintf(m.note, sizeof(m.note), "%s%s", t->coarse.note.c_str(), t->boxes.note.c_str());
         m.box_queries_cut = t->d_boxes ? t->box_queries_cut : 0;
     }
     const uint32_t n = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(m));
@@ -1564,21 +1524,17 @@ int vrc_memory_usage2(vrc_caster *h, int32_t rank, vrc_memory2 *out) {
     return VRC_OK;
 }
 
+// the older, fixed struct: the fields it shares with vrc_memory2
 int vrc_memory_usage(vrc_caster *h, int32_t rank, vrc_memory *out) {
-    if (!h || !out || rank < 0 || rank > (int32_t)h->peers.size()) return VRC_ERR_INVALID_ARGUMENT;
-    const vrc_caster *q = rank == 0 ? h : h->peers[rank - 1];
+    if (!out) return VRC_ERR_INVALID_ARGUMENT;
+    vrc_memory2 m;
+    m.struct_size = sizeof(m);
+    VRC_TRY(vrc_memory_usage2(h, rank, &m));
     memset(out, 0, sizeof(*out));
-    const size_t npix = q->d_viewport ? (size_t)q->width * (size_t)std::max(q->buffer_rows, 1) : 0;
-    out->device = q->device;
-    out->rows = q->buffer_rows;
-    out->viewport_bytes = 16 * npix;
-    out->image_bytes = 16 * npix;
-    out->hit_bytes = q->d_hits ? 32 * npix : 0;
-    out->octree_bytes = q->d_desc ? q->n_desc * 8 + (q->d_attach_lookup ? q->n_desc * 4 + std::max<uint64_t>(q->n_attach, 1) * 8 : 0) : 0;
-    out->octree_shared = q->owns_desc ? 0 : 1;
-    out->peer_access = q->peer_access;
-    const vrc_tree *t = q->tree.get();
-    out->coarse_bytes = (t && t->d_coarse) ? (uint64_t)sizeof(uint64_t) << (3 * t->coarse_log2) : 0;
+    out->device = m.device; out->rows = m.rows;
+    out->viewport_bytes = m.viewport_bytes; out->image_bytes = m.image_bytes; out->hit_bytes = m.hit_bytes; out->octree_bytes = m.octree_bytes;
+    out->octree_shared = m.octree_shared; out->peer_access = m.peer_access;
+    out->coarse_bytes = m.coarse_bytes;
     return VRC_OK;
 }
 
@@ -1693,13 +1649,6 @@ int vrc_timing_get(vrc_caster *h, uint64_t *n_launches, double *total_kernel_ms)
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// the caller's current device, put back on every path out of a query (a group handle's queries run on rank 0's GPU)
-struct DeviceRestore {
-    int dev = -1;
-    DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
-    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
-
 // the argument and readiness checks both calls share; nothing is launched when one fails
 int query_check(vrc_caster *h, const void *rays, int64_t n, int32_t max_steps, uint32_t flags, const void *out, const char *what) {
     if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
@@ -1707,7 +1656,7 @@ int query_check(vrc_caster *h, const void *rays, int64_t n, int32_t max_steps, u
     if (flags & ~(uint32_t)VRC_RAY_AS_PIXEL) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_RAY_AS_PIXEL));
     if (n > 0 && (!rays || !out)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null rays or output", what);
     if (!h->validated) return fail(h, VRC_ERR_NOT_READY, "%s: validate() has not succeeded", what);
-    if (!h->have_octree || !h->tree || !h->tree->d_desc) return fail(h, VRC_ERR_NOT_READY, "%s: no octree assigned", what);
+    if (!h->tree) return fail(h, VRC_ERR_NOT_READY, "%s: no octree assigned", what);
     const int n2 = log2_exact(setting_or(h, "octree_dimensions", 0));
     if (n2 < 1 || n2 > vrc::kMaxLevels) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: octree_dimensions must be a power of two in [2, 2^%d]", what, vrc::kMaxLevels);
     const int64_t root = setting_or(h, "octree_root_index", 0);
@@ -1727,41 +1676,79 @@ bool query_pointer_ok(const vrc_caster *h, const void *p) {
     return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeUnified;
 }
 
-// One launch on the handle's stream (current device: h->device).  The tree's guard is held until the kernel is enqueued, as a
-// frame holds it; the coarse table and the empty boxes are used when vrc_prepare / validate / a frame has built them for this
-// tree, never built here.
-int query_enqueue(vrc_caster *h, const float *d_rays, int64_t n, int32_t max_steps, uint32_t flags, int32_t *d_out) {
-    std::unique_lock<std::mutex> lock(h->tree->guard);
-    mirror_tree(h);
-    vrc::QueryParams q;
-    memset(&q, 0, sizeof(q));
-    q.rays = d_rays; q.out = d_out; q.n = n; q.flags = flags;
-    const bool svo = setting_or(h, "using_octree", 0) == 0;
-    const int n2 = log2_exact(setting_or(h, "octree_dimensions", 0));
-    const uint64_t root = (uint64_t)setting_or(h, "octree_root_index", 0);
-    q.svo = svo ? 1 : 0;
-    q.octree_bias = (int32_t)setting_or(h, "octree_bias", 1);
-    q.descriptors = h->d_desc; q.root_index = root; q.log2_dim = n2;
-    if (svo) {
-        q.map_dim[0] = q.map_dim[1] = q.map_dim[2] = 1 << n2;
-        q.attach_lookup = (h->d_attach_lookup && h->d_attach) ? h->d_attach_lookup : nullptr;
-        q.attachments = q.attach_lookup ? h->d_attach : nullptr;
+// work the host queued on the null stream (a torch tensor's fill, say) comes first: the handle's stream does not wait for it by itself
+int wait_for_null_stream(vrc_caster *h) {
+    hipEvent_t ready = nullptr;
+    HIP_TRY(h, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ready, nullptr);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ready, 0);
+    (void)hipEventDestroy(ready);
+    HIP_TRY(h, e);
+    return VRC_OK;
+}
+
+// Grow device buffers that share one capacity (staging and scratch grow on demand; freed by the release_* calls, destroy).  A frame
+// in flight must not lose buffers it does not use anyway: the stream is drained first.
+struct GrowBuffer {
+    void **p; size_t bytes;
+    template <class T> GrowBuffer(T *&ptr, size_t n) : p((void **)&ptr), bytes(n) {}
+};
+template <class Cap>
+int grow(vrc_caster *h, Cap &have, Cap want, std::initializer_list<GrowBuffer> buffers) {
+    if (have >= want) return VRC_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (const GrowBuffer &b : buffers)
+        if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; }
+    have = 0;
+    for (const GrowBuffer &b : buffers) HIP_TRY(h, hipMalloc(b.p, b.bytes));
+    have = want;
+    return VRC_OK;
+}
+
+// The tree's table and boxes, if they were built for this root and depth.  The query paths use what vrc_prepare / validate / a
+// frame has built for the tree and never build themselves.  The caller holds t->guard.
+bool coarse_for(const vrc_tree *t, uint64_t root, int n) {
+    const TableKey &k = t->coarse.built;
+    return t->d_coarse && k.root == root && k.depth == n && k.log2 >= 1 && k.log2 <= n - 2;
+}
+bool boxes_for(const vrc_tree *t, uint64_t root, int n) {
+    return coarse_for(t, root, n) && t->d_boxes && t->d_box_aux && t->boxes.built.at == t->coarse.built;
+}
+
+// The scene a ray or a box query runs against: the fields QueryParams and BoxParams name alike, from the handle's settings and its
+// tree.  The caller holds t->guard.
+template <class P>
+void bind_scene(const vrc_caster *h, const vrc_tree *t, P &q) {
+    q.svo = setting_or(h, "using_octree", 0) == 0 ? 1 : 0;
+    q.descriptors = t->d_desc;
+    q.root_index = (uint64_t)setting_or(h, "octree_root_index", 0);
+    q.log2_dim = log2_exact(setting_or(h, "octree_dimensions", 0));
+    if (q.svo) {
+        q.map_dim[0] = q.map_dim[1] = q.map_dim[2] = 1 << q.log2_dim;
+        bind_attachments(t, q);
+        if (setting_or(h, "coarse_log2", -1) != 0 && coarse_for(t, q.root_index, q.log2_dim)) { q.coarse = t->d_coarse; q.coarse_log2 = t->coarse.built.log2; }
     } else {
         for (int a = 0; a < 3; a++) q.map_dim[a] = h->map_dim[a];
         q.map = h->d_map;
         q.map_bytes = (uint64_t)h->map_dim[0] * (uint64_t)h->map_dim[1] * (uint64_t)h->map_dim[2];
     }
+}
+
+// One launch on the handle's stream (current device: h->device).  The tree's guard is held until the kernel is enqueued, as a
+// frame holds it.
+int query_enqueue(vrc_caster *h, const float *d_rays, int64_t n, int32_t max_steps, uint32_t flags, int32_t *d_out) {
+    vrc_tree *t = h->tree.get();
+    std::unique_lock<std::mutex> lock(t->guard);
+    vrc::QueryParams q;
+    memset(&q, 0, sizeof(q));
+    q.rays = d_rays; q.out = d_out; q.n = n; q.flags = flags;
+    q.octree_bias = (int32_t)setting_or(h, "octree_bias", 1);
+    bind_scene(h, t, q);
     // max_steps = 0: no cap below the map's edge -- every iteration steps an axis, so 3 dim + 3 bounds a ray that starts inside
     const int64_t dim_max = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
     q.cap = max_steps > 0 ? max_steps : (int32_t)std::min<int64_t>(INT32_MAX, 3 * dim_max + 3);
-    const vrc_tree *t = h->tree.get();
-    if (svo && setting_or(h, "coarse_log2", -1) != 0 && t->d_coarse && t->coarse_root == root && t->coarse_depth == n2 &&
-        t->coarse_log2 >= 1 && t->coarse_log2 <= n2 - 2) {
-        q.coarse = t->d_coarse; q.coarse_log2 = t->coarse_log2;
-        if (setting_or(h, "empty_boxes", -1) != 0 && t->d_boxes && t->d_box_aux && t->box_log2 == t->coarse_log2 && t->box_root == root &&
-            t->box_depth == n2) {
-            q.boxes = t->d_boxes; q.box_aux = t->d_box_aux; q.box_child = t->d_box_child; q.box_levels = t->box_levels;
-        }
+    if (q.coarse && setting_or(h, "empty_boxes", -1) != 0 && boxes_for(t, q.root_index, q.log2_dim)) {
+        q.boxes = t->d_boxes; q.box_aux = t->d_box_aux; q.box_child = t->d_box_child; q.box_levels = t->box_levels;
     }
     HIP_TRY(h, vrc::launch_raycast_query(q, h->stream));
     return VRC_OK;
@@ -1777,17 +1764,9 @@ int vrc_cast_rays(vrc_caster *h, const float *rays, int64_t n, int32_t max_steps
     if (rc != VRC_OK || n == 0) return rc;
     DeviceRestore restore;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->query_capacity < n) {                                   // staging grows on demand (freed by the release_* calls, destroy)
-        HIP_TRY(h, hipStreamSynchronize(h->stream));               // (a frame in flight must not lose buffers it does not use anyway)
-        release(h->d_query_rays); release(h->d_query_out);
-        h->query_capacity = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_query_rays, sizeof(float) * 6 * (size_t)n));
-        HIP_TRY(h, hipMalloc((void **)&h->d_query_out, sizeof(int32_t) * 8 * (size_t)n));
-        h->query_capacity = n;
-    }
+    VRC_TRY(grow(h, h->query_capacity, n, {{h->d_query_rays, sizeof(float) * 6 * (size_t)n}, {h->d_query_out, sizeof(int32_t) * 8 * (size_t)n}}));
     HIP_TRY(h, hipMemcpyAsync(h->d_query_rays, rays, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    rc = query_enqueue(h, h->d_query_rays, n, max_steps, flags, h->d_query_out);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(query_enqueue(h, h->d_query_rays, n, max_steps, flags, h->d_query_out));
     HIP_TRY(h, hipMemcpyAsync(out, h->d_query_out, sizeof(int32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return VRC_OK;
@@ -1802,15 +1781,8 @@ int vrc_cast_rays_device(vrc_caster *h, const void *d_rays, int64_t n, int32_t m
     HIP_TRY(h, hipSetDevice(h->device));
     if (!query_pointer_ok(h, d_rays) || !query_pointer_ok(h, d_out))
         return fail(h, VRC_ERR_INVALID_ARGUMENT, "cast_rays_device: rays and output must be memory the GPU of the handle (device %d) can read and write", h->device);
-    // work the host queued on the null stream (a torch tensor's fill, say) comes first: the handle's stream does not wait for it by itself
-    hipEvent_t ready = nullptr;
-    HIP_TRY(h, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ready, nullptr);
-    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ready, 0);
-    (void)hipEventDestroy(ready);
-    HIP_TRY(h, e);
-    rc = query_enqueue(h, static_cast<const float *>(d_rays), n, max_steps, flags, static_cast<int32_t *>(d_out));
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(wait_for_null_stream(h));
+    VRC_TRY(query_enqueue(h, static_cast<const float *>(d_rays), n, max_steps, flags, static_cast<int32_t *>(d_out)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return VRC_OK;
 }
@@ -1836,70 +1808,31 @@ int box_check(vrc_caster *h, const void *boxes, int64_t n, int32_t max_voxels, u
     return query_check(h, boxes, n, 0, 0, records, what);
 }
 
-// grow a device buffer to `bytes` (a frame in flight must not lose buffers it does not use anyway: the stream is drained first)
-template <class T>
-int grow(vrc_caster *h, T *&p, size_t &have, size_t bytes) {
-    if (have >= bytes) return VRC_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    release(p);
-    have = 0;
-    HIP_TRY(h, hipMalloc((void **)&p, bytes));
-    have = bytes;
-    return VRC_OK;
-}
-
 // Plan, scans, count, (scan, emit), finalize on the handle's stream (current device: h->device).  The tree's guard is held
 // throughout, as query_enqueue holds it; the coarse table is used when vrc_prepare / validate / a frame has built it for this
 // tree, never built here.  One host wait in the middle: the item totals size the grid and the per-item scratch.
 int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags, int32_t *d_rec, int64_t *d_cnt,
                 int32_t *d_vox) {
     std::unique_lock<std::mutex> lock(h->tree->guard);
-    mirror_tree(h);
     vrc::BoxParams q;
     memset(&q, 0, sizeof(q));
     q.boxes = d_boxes; q.n = n; q.max_voxels = max_voxels; q.flags = flags;
     q.records = d_rec; q.counts = d_cnt; q.voxels = max_voxels > 0 ? d_vox : nullptr;
-    const bool svo = setting_or(h, "using_octree", 0) == 0;
-    const int n2 = log2_exact(setting_or(h, "octree_dimensions", 0));
-    const uint64_t root = (uint64_t)setting_or(h, "octree_root_index", 0);
-    q.svo = svo ? 1 : 0;
-    q.descriptors = h->d_desc; q.root_index = root; q.log2_dim = n2;
-    if (svo) {
-        q.map_dim[0] = q.map_dim[1] = q.map_dim[2] = 1 << n2;
-        q.space_log2 = n2;
-        q.attach_lookup = (h->d_attach_lookup && h->d_attach) ? h->d_attach_lookup : nullptr;
-        q.attachments = q.attach_lookup ? h->d_attach : nullptr;
-        const vrc_tree *t = h->tree.get();
-        if (setting_or(h, "coarse_log2", -1) != 0 && t->d_coarse && t->coarse_root == root && t->coarse_depth == n2 &&
-            t->coarse_log2 >= 1 && t->coarse_log2 <= n2 - 2) {
-            q.coarse = t->d_coarse; q.coarse_log2 = t->coarse_log2;
-        }
-    } else {
-        for (int a = 0; a < 3; a++) q.map_dim[a] = h->map_dim[a];
-        q.map = h->d_map;
-        q.map_bytes = (uint64_t)h->map_dim[0] * (uint64_t)h->map_dim[1] * (uint64_t)h->map_dim[2];
-        const int32_t side = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
-        q.space_log2 = 1;
-        while ((1 << q.space_log2) < side) q.space_log2++;
-    }
+    bind_scene(h, h->tree.get(), q);
+    // the aligned space the items tile: the tree's, or the map's largest side rounded up
+    const int32_t side = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
+    q.space_log2 = 1;
+    while ((1 << q.space_log2) < side) q.space_log2++;
     // per-box scratch: plan, the two item counts and their scans, the totals, the corners
-    if (h->box_capacity < n) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        release(h->d_box_plan); release(h->d_box_scan); release(h->d_box_corner);
-        h->box_capacity = 0;
-        HIP_TRY(h, hipMalloc(&h->d_box_plan, sizeof(vrc::BoxPlan) * (size_t)n));
-        HIP_TRY(h, hipMalloc((void **)&h->d_box_scan, sizeof(int64_t) * 5 * (size_t)n));
-        HIP_TRY(h, hipMalloc((void **)&h->d_box_corner, sizeof(int32_t) * 6 * (size_t)n));
-        h->box_capacity = n;
-    }
+    VRC_TRY(grow(h, h->box_capacity, n, {{h->d_box_plan, sizeof(vrc::BoxPlan) * (size_t)n}, {h->d_box_scan, sizeof(int64_t) * 5 * (size_t)n},
+                                         {h->d_box_corner, sizeof(int32_t) * 6 * (size_t)n}}));
     int64_t *small_cnt = h->d_box_scan, *big_cnt = h->d_box_scan + n;
     q.plan = static_cast<vrc::BoxPlan *>(h->d_box_plan);
     q.small_end = h->d_box_scan + 2 * n; q.big_end = h->d_box_scan + 3 * n; q.acc_count = h->d_box_scan + 4 * n;
     q.acc_corner = h->d_box_corner;
     size_t need = 0;
     HIP_TRY(h, vrc::box_scan(nullptr, &need, small_cnt, q.small_end, n, h->stream));
-    int rc = grow(h, h->d_box_temp, h->box_temp_bytes, need);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(grow(h, h->box_temp_bytes, need, {{h->d_box_temp, need}}));
     HIP_TRY(h, vrc::launch_box_plan(q, small_cnt, big_cnt, h->stream));
     size_t bytes = h->box_temp_bytes;
     HIP_TRY(h, vrc::box_scan(h->d_box_temp, &bytes, small_cnt, q.small_end, n, h->stream));
@@ -1914,18 +1847,11 @@ int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxe
     const bool emit = max_voxels > 0 && items > 0;
     if (emit) {
         // per-item counts and their scan (an item's list offset inside its box)
-        if (h->box_item_capacity < items) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            release(h->d_box_items);
-            h->box_item_capacity = 0;
-            HIP_TRY(h, hipMalloc((void **)&h->d_box_items, sizeof(int64_t) * 2 * (size_t)items));
-            h->box_item_capacity = items;
-        }
+        VRC_TRY(grow(h, h->box_item_capacity, items, {{h->d_box_items, sizeof(int64_t) * 2 * (size_t)items}}));
         q.item_count = h->d_box_items; q.item_end = h->d_box_items + items;
         need = 0;
         HIP_TRY(h, vrc::box_scan(nullptr, &need, q.item_count, q.item_end, items, h->stream));
-        rc = grow(h, h->d_box_temp, h->box_temp_bytes, need);
-        if (rc != VRC_OK) return rc;
+        VRC_TRY(grow(h, h->box_temp_bytes, need, {{h->d_box_temp, need}}));
     }
     HIP_TRY(h, vrc::launch_box_count(q, 0, h->stream));
     if (emit) {
@@ -1948,25 +1874,14 @@ int vrc_box_intersection(vrc_caster *h, const float *boxes, int64_t n, int32_t m
     if (rc != VRC_OK || n == 0) return rc;
     DeviceRestore restore;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->box_io_capacity < n) {                                  // staging grows on demand (freed by the release_* calls, destroy)
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        release(h->d_box_in); release(h->d_box_rec); release(h->d_box_cnt);
-        h->box_io_capacity = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_box_in, sizeof(float) * 6 * (size_t)n));
-        HIP_TRY(h, hipMalloc((void **)&h->d_box_rec, sizeof(int32_t) * 8 * (size_t)n));
-        HIP_TRY(h, hipMalloc((void **)&h->d_box_cnt, sizeof(int64_t) * (size_t)n));
-        h->box_io_capacity = n;
-    }
+    VRC_TRY(grow(h, h->box_io_capacity, n, {{h->d_box_in, sizeof(float) * 6 * (size_t)n}, {h->d_box_rec, sizeof(int32_t) * 8 * (size_t)n},
+                                        {h->d_box_cnt, sizeof(int64_t) * (size_t)n}}));
     const size_t vox_bytes = (size_t)n * (size_t)max_voxels * 16u;
-    if (vox_bytes) {
-        rc = grow(h, h->d_box_vox, h->box_vox_bytes, vox_bytes);
-        if (rc != VRC_OK) return rc;
-    }
+    if (vox_bytes) VRC_TRY(grow(h, h->box_vox_bytes, vox_bytes, {{h->d_box_vox, vox_bytes}}));
     HIP_TRY(h, hipMemcpyAsync(h->d_box_in, boxes, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, h->stream));
     // the list goes down first: the entries a box does not write come back as the caller left them
     if (vox_bytes) HIP_TRY(h, hipMemcpyAsync(h->d_box_vox, voxels, vox_bytes, hipMemcpyHostToDevice, h->stream));
-    rc = box_enqueue(h, h->d_box_in, n, max_voxels, flags, h->d_box_rec, h->d_box_cnt, h->d_box_vox);
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(box_enqueue(h, h->d_box_in, n, max_voxels, flags, h->d_box_rec, h->d_box_cnt, h->d_box_vox));
     HIP_TRY(h, hipMemcpyAsync(records, h->d_box_rec, sizeof(int32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(counts, h->d_box_cnt, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     if (vox_bytes) HIP_TRY(h, hipMemcpyAsync(voxels, h->d_box_vox, vox_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1986,16 +1901,9 @@ int vrc_box_intersection_device(vrc_caster *h, const void *d_boxes, int64_t n, i
     HIP_TRY(h, hipSetDevice(h->device));
     if (!query_pointer_ok(h, d_boxes) || !query_pointer_ok(h, d_records) || !query_pointer_ok(h, d_counts) || (list && !query_pointer_ok(h, d_voxels)))
         return fail(h, VRC_ERR_INVALID_ARGUMENT, "box_intersection_device: boxes and outputs must be memory the GPU of the handle (device %d) can read and write", h->device);
-    // work the host queued on the null stream (a torch tensor's fill, say) comes first: the handle's stream does not wait for it by itself
-    hipEvent_t ready = nullptr;
-    HIP_TRY(h, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ready, nullptr);
-    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, ready, 0);
-    (void)hipEventDestroy(ready);
-    HIP_TRY(h, e);
-    rc = box_enqueue(h, static_cast<const float *>(d_boxes), n, max_voxels, flags, static_cast<int32_t *>(d_records),
-                     static_cast<int64_t *>(d_counts), static_cast<int32_t *>(d_voxels));
-    if (rc != VRC_OK) return rc;
+    VRC_TRY(wait_for_null_stream(h));
+    VRC_TRY(box_enqueue(h, static_cast<const float *>(d_boxes), n, max_voxels, flags, static_cast<int32_t *>(d_records),
+                        static_cast<int64_t *>(d_counts), static_cast<int32_t *>(d_voxels)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return VRC_OK;
 }
