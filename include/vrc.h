@@ -408,6 +408,57 @@ int vrc_box_intersection(vrc_caster *h, const float *boxes, int64_t n, int32_t m
 int vrc_box_intersection_device(vrc_caster *h, const void *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags,
                                 void *d_records, void *d_counts, void *d_voxels);
 
+/* ---- swept-box queries --------------------------------------------------- */
+
+/* How far can a box move before it touches something, and which face stops it?  Map::ShortRayIntersection
+ * (include/map/Map.h:53, a stub in the reference) and the "collision result" its design note asks for: the move of a player,
+ * a falling object or a projectile with volume, per tick -- with the contact normal that move-and-slide needs, and no
+ * tunnelling through thin walls.
+ *
+ * A sweep is 9 floats: origin o, extent m (the box of vrc_box_intersection) and displacement d.  The box [o, o + m) moves to
+ * [o + d, o + m + d) over t in [0, 1).  Which voxels count (VRC_SWEEP_STOPPING_ONLY = VRC_BOX_STOPPING_ONLY), which branch is
+ * read, the materials, solid leaves above the bottom and out-of-map-is-empty are exactly vrc_box_intersection's rules above.
+ *
+ * The answer is defined by events, in float32 operations (unfused, IEEE divide, subnormals kept), so it can be replayed bit
+ * for bit (tests/sweep_replay.py):
+ *   start   per axis e = o + m rounded to float32, lo = floor(o), hi = max(ceil(e), lo + 1): the box query's range.  If that
+ *           range, clipped to the map, holds a counted voxel: START_SOLID, t = 0, no normal, the voxel is the first counted
+ *           voxel of the range in Morton order (the box query's list order), with its material.
+ *   events  an axis moves iff d != 0.  With s = sign(d), its next leading event (the box enters a layer) is at
+ *           t = ((float)hi - e) / d entering layer hi (s > 0), t = (o - (float)lo) / (-d) entering layer lo - 1 (s < 0); its
+ *           next trailing event (the box leaves a layer) at t = ((float)(lo + 1) - o) / d leaving layer lo (s > 0),
+ *           t = (e - (float)(hi - 1)) / (-d) leaving layer hi - 1 (s < 0) -- always from the current integer bound.  The event
+ *           with the smallest t is next; ties: trailing before leading, then x < y < z.  No event, or not t < 1: the move is
+ *           free, t = 1.  A trailing event shrinks the range by its layer.  A leading event tests the one-layer slab it enters
+ *           (the current ranges of the other two axes, clipped to the map) and then extends the range; a counted voxel in the
+ *           slab is a HIT: t = the event's time, normal code -s (a + 1) (+-1 x, +-2 y, +-3 z: the face normal of the blocking
+ *           voxel, opposite to the motion), the voxel is the slab's first counted voxel in Morton order, with its material.
+ *           A box resting on a face and moving into it hits at t = 0; moving along the face it does not touch the voxels below.
+ *   stops   checked after the start test and after every event.  LEFT_MAP: on some axis hi <= 0 with d <= 0, or lo >= dim
+ *           with d >= 0 (nothing can be met any more): free, t = 1.  EVENT_CAP: the next event has t < 1 but `cap` events
+ *           were processed: t = the last processed event's time; cap = max_events, or 2 (dim_x + dim_y + dim_z) + 64 when
+ *           max_events = 0.  CLIPPED: at the start or after some event a bound lay outside the map.
+ *   REJECTED  what the box query rejects, a non-finite d, or |o + d| or |e + d| >= 2^30 (sums rounded to float32): flags only.
+ *
+ * Per sweep i, records[8 i + 0] VRC_SWEEP_* flags, [1] normal code (0: none), [2] the float bits of t, [3..5] the blocking
+ * voxel (-1: none), [6] its material (0: none), [7] events processed (the event that hits included).  A rejected sweep has
+ * t bits 0.
+ *
+ * Host rules as vrc_box_intersection: synchronous on the handle's stream, frame state and vrc_last_kernel untouched, the
+ * coarse table used when it is built and never built here, rank 0's GPU for a group, the caller's device restored, staging
+ * and scratch grown on demand and freed by vrc_release_map / _octree / _viewport and vrc_destroy, device pointers 4-byte
+ * aligned.  Errors, with nothing launched: VRC_ERR_INVALID_ARGUMENT for a null handle or pointer, n < 0, max_events < 0,
+ * unknown flag bits or misalignment; VRC_ERR_NOT_READY as for ray queries.  n = 0 succeeds.                              */
+#define VRC_SWEEP_STOPPING_ONLY 1u     /* flag: only materials 5 and 6 block (vrc_cast_rays' rule); default: any non-zero material */
+#define VRC_SWEEP_HIT          1       /* record[0] bits */
+#define VRC_SWEEP_START_SOLID  2
+#define VRC_SWEEP_CLIPPED      4
+#define VRC_SWEEP_REJECTED     8
+#define VRC_SWEEP_EVENT_CAP   16
+#define VRC_SWEEP_LEFT_MAP    32
+int vrc_sweep_boxes(vrc_caster *h, const float *sweeps, int64_t n, int32_t max_events, uint32_t flags, int32_t *records);
+int vrc_sweep_boxes_device(vrc_caster *h, const void *d_sweeps, int64_t n, int32_t max_events, uint32_t flags, void *d_records);
+
 /* Device pointers of the resident frame buffers (float4[w*h], int32[8*w*h]);
  * lets a host that owns the GPU (e.g. a torch process) consume the frame
  * without a PCIe round trip.                                                 */

@@ -179,6 +179,8 @@ SIGNATURES = {
     "vrc_cast_rays_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrc_box_intersection": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p, C.POINTER(C.c_int64), _i32p]),
     "vrc_box_intersection_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrc_sweep_boxes": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p]),
+    "vrc_sweep_boxes_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
@@ -189,6 +191,9 @@ RAY_HIT, RAY_LEFT_MAP, RAY_STEP_CAP, RAY_REJECTED = 1, 2, 4, 8
 # box queries (vrc_box_intersection): the flag, and the bits of record field 0
 BOX_STOPPING_ONLY = 1
 BOX_ANY, BOX_TRUNCATED, BOX_CLIPPED, BOX_REJECTED = 1, 2, 4, 8
+# swept-box queries (vrc_sweep_boxes): the flag, and the bits of record field 0
+SWEEP_STOPPING_ONLY = 1
+SWEEP_HIT, SWEEP_START_SOLID, SWEEP_CLIPPED, SWEEP_REJECTED, SWEEP_EVENT_CAP, SWEEP_LEFT_MAP = 1, 2, 4, 8, 16, 32
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype = _res
@@ -788,6 +793,26 @@ class CLCaster:
         return self._ok(lib.vrc_box_intersection_device(self._h, C.c_void_p(boxes_ptr), int(n), int(max_voxels),
                                                         BOX_STOPPING_ONLY if stopping_only else 0, C.c_void_p(records_ptr),
                                                         C.c_void_p(counts_ptr), C.c_void_p(voxels_ptr or None)))
+
+    # -- swept-box queries (vrc_sweep_boxes, include/vrc.h)
+    def sweep_boxes(self, sweeps: np.ndarray, max_events: int = 0, stopping_only: bool = False) -> np.ndarray:
+        """How far each box moves before it touches a counted voxel: sweeps (n, 9) float32 = origin xyz, extent xyz,
+        displacement xyz -> records (n, 8) int32 = SWEEP_* flags, normal code (+-1 x, +-2 y, +-3 z, 0 none), float bits of t
+        (records[:, 2].view(np.float32)), blocking voxel xyz (-1 none), its material, events processed."""
+        s = np.ascontiguousarray(sweeps, dtype=np.float32)
+        if s.ndim != 2 or s.shape[1] != 9:
+            raise VrcError(f"sweep_boxes: sweeps must have shape (n, 9), got {s.shape}")
+        n = s.shape[0]
+        records = np.empty((n, 8), dtype=np.int32)
+        if not self._ok(lib.vrc_sweep_boxes(self._h, _ptr(s, _f32p), n, int(max_events), SWEEP_STOPPING_ONLY if stopping_only else 0,
+                                            _ptr(records, _i32p))):
+            raise VrcError(self.last_error())
+        return records
+
+    def sweep_boxes_device(self, sweeps_ptr: int, n: int, records_ptr: int, max_events: int = 0, stopping_only: bool = False) -> bool:
+        """sweep_boxes on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 9 float32 in, n x 8 int32 out)."""
+        return self._ok(lib.vrc_sweep_boxes_device(self._h, C.c_void_p(sweeps_ptr), int(n), int(max_events),
+                                                   SWEEP_STOPPING_ONLY if stopping_only else 0, C.c_void_p(records_ptr)))
 
     def counters(self) -> dict:
         c = Counters()

@@ -26,7 +26,8 @@ struct BoxPlan {
 };
 
 struct BoxParams {
-    const float *boxes;               // float[6 * n]: origin xyz, extent xyz
+    const float *boxes;               // float[box_stride * n]: origin xyz, extent xyz (then what a sweep adds: box_sweep.h)
+    int32_t box_stride;               // 6 for a box query
     int64_t n;
     int32_t max_voxels;
     uint32_t flags;                   // kBoxStoppingOnly

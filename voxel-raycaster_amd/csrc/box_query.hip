@@ -14,17 +14,14 @@
 //   box_query_count_kernel     pass 1: items whose offset is below max_voxels walk again and write their voxels in Morton order
 //   box_query_finalize_kernel  one lane per box: records and counts, with plain stores
 //
-// The walk (SVO branch) descends from the coarse table's cell (or the root) to the walk's node, then visits the node's subtree
-// in Morton order with a restart at every finished node -- stackless, so no LDS and no scratch.  Empty slots and slots outside
-// the box are skipped; a solid leaf (a valid leaf slot at any level, or any valid slot at the bottom level: query_locate's
-// rule, raycast_query.hip) is counted by volume; a solid cube that the box cuts is entered as a virtual node only to emit, so
-// its first k voxels in Morton order come without visiting the rest.  The array branch walks the same nodes over the map's
-// bytes.
+// The walk itself (stackless, Morton order, restricted to the box) is box_walk.hpp's, shared with the swept-box queries
+// (box_sweep.hip), which also run these passes over their start boxes (box_stride 9, a list of one voxel).
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_scan.hpp>
 
 #include "box_query.h"
+#include "box_walk.hpp"
 #include "vrc_launch.h"
 #include "vrc_params.h"
 
@@ -32,177 +29,14 @@ namespace vrc {
 
 namespace {
 
-// the packed cursor entry of raycast_query.hip's query_entry: bits 0-7 valid mask, 8-15 leaf mask, 16-63 index of the first kept child
-__device__ __forceinline__ uint64_t box_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);
-}
-
-// length of [c, c + s) inside [lo, hi)
-__device__ __forceinline__ int overlap(int c, int s, int lo, int hi) {
-    const int a = c > lo ? c : lo, b = c + s < hi ? c + s : hi;
-    return b > a ? b - a : 0;
-}
-
-// coordinate `axis` of Morton index t (bit 3k + axis -> bit k)
-__device__ __forceinline__ int morton_coord(uint64_t t, int axis) {
-    int v = 0;
-    for (int k = 0; k < 21; k++) v |= (int)((t >> (3 * k + axis)) & 1ULL) << k;
-    return v;
-}
-
-struct Range { int lo[3], hi[3]; };
-struct Acc { int64_t count; int mn[3], mx[3]; };
-
-__device__ __forceinline__ bool counted(const BoxParams &q, int mat) {
-    return (q.flags & kBoxStoppingOnly) ? (mat == 5 || mat == 6) : mat != 0;
-}
-
-// the node of size 2^r at (cx, cy, cz) (r >= 1): 0 empty, 1 inside a solid leaf, 2 a descriptor (cur, its index)
-__device__ int region_descend(const BoxParams &q, int cx, int cy, int cz, int r, uint64_t &cur, uint64_t &cur_index) {
-    const int n = q.log2_dim;
-    int top;
-    cur_index = q.root_index;
-    if (q.coarse && r <= n - q.coarse_log2) {
-        const int csh = n - q.coarse_log2;
-        const uint64_t e = q.coarse[coarse_index((unsigned)(cx >> csh), (unsigned)(cy >> csh), (unsigned)(cz >> csh), q.coarse_log2)];
-        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
-        top = (int)(e >> kCoarseLevelShift);
-    } else {
-        cur = box_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
-        top = 0;
+// the list of a box: entry k at out + 4 k
+struct ListSink {
+    int32_t *__restrict__ out;
+    __device__ __forceinline__ void operator()(int64_t at, int x, int y, int z, int mat) const {
+        int32_t *e = out + 4 * at;
+        e[0] = x; e[1] = y; e[2] = z; e[3] = mat;
     }
-    for (int guard = 0; guard <= n && n - top > r; guard++) {
-        const int b = n - top - 1;                        // (>= r >= 1: the child is never a single voxel)
-        const int i = ((cx >> b) & 1) | (((cy >> b) & 1) << 1) | (((cz >> b) & 1) << 2);
-        const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
-        if (!(masks & bit)) return 0;
-        if ((masks >> 8) & bit) return 1;
-        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
-        cur_index = (cur >> 16) + (uint64_t)rank;
-        cur = box_entry(q.descriptors, cur_index, q.descriptors[cur_index]);
-        top++;
-    }
-    return 2;
-}
-
-// Walk the node of size 2^r (r >= 1) at (cx, cy, cz) restricted to the range, in Morton order.  kEmit = false: count and
-// corners into acc.  kEmit = true: write entry base + (voxels counted so far) to `out` while it is below `limit`.
-template <bool kEmit>
-__device__ void walk(const BoxParams &q, int cx, int cy, int cz, int r, const Range &rg, Acc &acc, int64_t base, int64_t limit,
-                     int32_t *__restrict__ out) {
-    uint64_t cur0 = 0, idx0 = 0;
-    const int state0 = q.svo ? region_descend(q, cx, cy, cz, r, cur0, idx0) : 2;
-    if (state0 == 0) return;
-    const uint64_t end = 1ULL << (3 * r);
-    uint64_t p = 0;
-    while (p < end) {
-        // descend from the walk's node toward p (a restart: the node that held p's predecessor is finished)
-        uint64_t cur = cur0, cur_index = idx0;
-        bool solid = state0 == 1;
-        int b = r, ox = cx, oy = cy, oz = cz;
-        while (true) {
-            const int cb = b - 1, s = 1 << cb;
-            const int i = (int)((p >> (3 * cb)) & 7ULL);
-            const int x0 = ox + (i & 1) * s, y0 = oy + ((i >> 1) & 1) * s, z0 = oz + ((i >> 2) & 1) * s;
-            const int wx = overlap(x0, s, rg.lo[0], rg.hi[0]), wy = overlap(y0, s, rg.lo[1], rg.hi[1]), wz = overlap(z0, s, rg.lo[2], rg.hi[2]);
-            if (wx && wy && wz) {
-                int kind = 0, mat = 5;                    // 0 empty, 1 solid, 2 a node to enter
-                uint64_t child = 0;
-                if (!q.svo) {
-                    if (cb > 0) {
-                        kind = 2;
-                    } else {
-                        // the frame's index (y stride map_dim[2]); past the array reads as empty (raycast_query.hip)
-                        const uint64_t idx = (uint64_t)((long)x0 + (long)q.map_dim[0] * ((long)y0 + (long)q.map_dim[2] * z0));
-                        mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
-                        kind = 1;
-                    }
-                } else if (solid) {
-                    kind = 1;
-                } else {
-                    const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
-                    if (masks & bit) {
-                        if (((masks >> 8) & bit) || cb == 0) {
-                            kind = 1;
-                            if (q.attach_lookup && cb == 0) {        // only bottom-level descriptors carry materials
-                                const uint64_t a = q.attachments[q.attach_lookup[cur_index]];
-                                mat = (int)(int8_t)(a >> (8 * i));
-                            }
-                        } else {
-                            kind = 2;
-                            child = (cur >> 16) + (uint64_t)((unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u);
-                        }
-                    }
-                }
-                const bool whole = wx == s && wy == s && wz == s;
-                if (kind == 1 && kEmit && !whole) kind = 3;    // a solid cube the box cuts: entered virtually, to emit in order
-                if (kind >= 2) {
-                    if (kind == 2 && q.svo) {
-                        cur = box_entry(q.descriptors, child, q.descriptors[child]);
-                        cur_index = child;
-                    }
-                    solid = solid || kind == 3;
-                    b = cb; ox = x0; oy = y0; oz = z0;
-                    continue;
-                }
-                if (kind == 1 && counted(q, mat)) {
-                    const int64_t vol = (int64_t)wx * wy * wz;
-                    if (kEmit) {
-                        // (whole: the cube lies in the box) its first voxels in Morton order
-                        const int64_t at = base + acc.count;
-                        const int64_t k = limit - at < vol ? limit - at : vol;
-                        for (int64_t t = 0; t < k; t++) {
-                            int32_t *e = out + 4 * (at + t);
-                            e[0] = x0 + morton_coord((uint64_t)t, 0);
-                            e[1] = y0 + morton_coord((uint64_t)t, 1);
-                            e[2] = z0 + morton_coord((uint64_t)t, 2);
-                            e[3] = mat;
-                        }
-                        acc.count += vol;
-                        if (base + acc.count >= limit) return;
-                    } else {
-                        acc.count += vol;
-                        const int lx = x0 > rg.lo[0] ? x0 : rg.lo[0], ly = y0 > rg.lo[1] ? y0 : rg.lo[1], lz = z0 > rg.lo[2] ? z0 : rg.lo[2];
-                        acc.mn[0] = min(acc.mn[0], lx); acc.mn[1] = min(acc.mn[1], ly); acc.mn[2] = min(acc.mn[2], lz);
-                        acc.mx[0] = max(acc.mx[0], lx + wx - 1); acc.mx[1] = max(acc.mx[1], ly + wy - 1); acc.mx[2] = max(acc.mx[2], lz + wz - 1);
-                    }
-                }
-            }
-            // the child is done: on to its next sibling, or (the last child) restart toward the next node
-            p = ((p >> (3 * cb)) + 1ULL) << (3 * cb);
-            if (i == 7) break;
-        }
-    }
-}
-
-// first box whose inclusive end is above item k
-__device__ int64_t owner(const int64_t *__restrict__ end, int64_t n, int64_t k) {
-    int64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (end[mid] > k) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// the j-th node (Morton order) of the node range [a, b) per axis, in a grid of 2^m nodes per axis
-__device__ void morton_select(int64_t j, const int a[3], const int b[3], int m, int c[3]) {
-    c[0] = c[1] = c[2] = 0;
-    for (int l = m - 1; l >= 0; l--) {
-        const int h = 1 << l;
-        int nx = c[0], ny = c[1], nz = c[2];
-        for (int o = 0; o < 8; o++) {
-            const int x0 = c[0] + (o & 1) * h, y0 = c[1] + ((o >> 1) & 1) * h, z0 = c[2] + ((o >> 2) & 1) * h;
-            const int64_t k = (int64_t)overlap(x0, h, a[0], b[0]) * overlap(y0, h, a[1], b[1]) * overlap(z0, h, a[2], b[2]);
-            nx = x0; ny = y0; nz = z0;
-            if (j < k) break;
-            j -= k;
-        }
-        c[0] = nx; c[1] = ny; c[2] = nz;
-    }
-}
+};
 
 struct ItemRef { int64_t box, first; int node[3]; Range rg; int s; };
 
@@ -252,7 +86,7 @@ __device__ __forceinline__ int64_t item_offset(const BoxParams &q, int64_t g, in
 __global__ __launch_bounds__(kBoxThreads) void box_query_plan_kernel(const BoxParams q, int64_t *__restrict__ small_cnt, int64_t *__restrict__ big_cnt) {
     const int64_t stride = (int64_t)gridDim.x * kBoxThreads;
     for (int64_t i = (int64_t)blockIdx.x * kBoxThreads + threadIdx.x; i < q.n; i += stride) {
-        const float *bx = q.boxes + 6 * i;
+        const float *bx = q.boxes + (int64_t)q.box_stride * i;
         BoxPlan pl;
         pl.s_log2 = 1; pl.kind = 0; pl.flags = 0;
         bool rej = false;
@@ -316,13 +150,16 @@ __global__ __launch_bounds__(kBoxThreads) void box_query_count_kernel(const BoxP
             Acc acc = {0, {INT32_MAX, INT32_MAX, INT32_MAX}, {-1, -1, -1}};
             const int cx = it.node[0] << it.s, cy = it.node[1] << it.s, cz = it.node[2] << it.s;
             if (pass == 0) {
-                walk<false>(q, cx, cy, cz, it.s, it.rg, acc, 0, 0, nullptr);
+                NoSink none;
+                walk<false>(q, cx, cy, cz, it.s, it.rg, acc, 0, 0, none);
                 add_to_box(q, it.box, acc);
                 if (q.item_count) q.item_count[k] = acc.count;
             } else if (q.item_count[k] > 0) {
                 const int64_t off = item_offset(q, k, it.first);
-                if (off < q.max_voxels)
-                    walk<true>(q, cx, cy, cz, it.s, it.rg, acc, off, q.max_voxels, q.voxels + (size_t)it.box * (size_t)q.max_voxels * 4u);
+                if (off < q.max_voxels) {
+                    ListSink list = {q.voxels + (size_t)it.box * (size_t)q.max_voxels * 4u};
+                    walk<true>(q, cx, cy, cz, it.s, it.rg, acc, off, q.max_voxels, list);
+                }
             }
         } else {
             // wave items: lane = the Morton index of the item's 4 x 4 x 4 sub-cube of 2^(s-2) voxels
@@ -333,8 +170,9 @@ __global__ __launch_bounds__(kBoxThreads) void box_query_count_kernel(const BoxP
             const int cy = (it.node[1] << it.s) + ((((lane >> 1) & 1) | ((lane >> 3) & 2)) << r);
             const int cz = (it.node[2] << it.s) + ((((lane >> 2) & 1) | ((lane >> 4) & 2)) << r);
             Acc acc = {0, {INT32_MAX, INT32_MAX, INT32_MAX}, {-1, -1, -1}};
+            NoSink none;
             if (pass == 0) {
-                walk<false>(q, cx, cy, cz, r, it.rg, acc, 0, 0, nullptr);
+                walk<false>(q, cx, cy, cz, r, it.rg, acc, 0, 0, none);
                 Acc tot;
                 tot.count = wave_sum(acc.count);
                 for (int x = 0; x < 3; x++) { tot.mn[x] = wave_min(acc.mn[x]); tot.mx[x] = wave_max(acc.mx[x]); }
@@ -346,7 +184,7 @@ __global__ __launch_bounds__(kBoxThreads) void box_query_count_kernel(const BoxP
                 if (q.item_count[g] <= 0) continue;               // (wave-uniform)
                 const int64_t off = item_offset(q, g, it.first);
                 if (off >= q.max_voxels) continue;
-                walk<false>(q, cx, cy, cz, r, it.rg, acc, 0, 0, nullptr);
+                walk<false>(q, cx, cy, cz, r, it.rg, acc, 0, 0, none);
                 // exclusive prefix of the lanes' counts: lane order is Morton order of the sub-cubes
                 int64_t incl = acc.count;
                 for (int o = 1; o < 64; o <<= 1) {
@@ -356,7 +194,8 @@ __global__ __launch_bounds__(kBoxThreads) void box_query_count_kernel(const BoxP
                 const int64_t at = off + incl - acc.count;
                 if (acc.count > 0 && at < q.max_voxels) {
                     Acc e = {0, {0, 0, 0}, {0, 0, 0}};
-                    walk<true>(q, cx, cy, cz, r, it.rg, e, at, q.max_voxels, q.voxels + (size_t)it.box * (size_t)q.max_voxels * 4u);
+                    ListSink list = {q.voxels + (size_t)it.box * (size_t)q.max_voxels * 4u};
+                    walk<true>(q, cx, cy, cz, r, it.rg, e, at, q.max_voxels, list);
                 }
             }
         }

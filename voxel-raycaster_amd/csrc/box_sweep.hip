@@ -1,0 +1,259 @@
+// box_sweep.hip -- batched swept-box queries against the resident scene (vrc_sweep_boxes, include/vrc.h) for gfx950: how far a
+// box moves before it touches a counted voxel, and which face stops it.
+//
+// The start boxes go through the box query's passes first (box_query.hip: plan, count, emit with a list of one voxel), so a
+// huge start box is already spread over many lanes and waves; the sweep kernels read "any + first voxel" from that.
+//
+//   box_sweep_plan_kernel   one lane per sweep: 1 where the sweep is a wave (a moving axis's face above lane_face_max voxels)
+//   (inclusive scan of those flags: wave k's sweep)
+//   box_sweep_lane_kernel   one lane per sweep: the event loop, each entered slab walked by the lane
+//   box_sweep_wave_kernel   one wave per sweep: the event state is the same in all 64 lanes; an entered slab is tiled by aligned
+//                           nodes which the lanes take in Morton order, the first voxel is the lowest lane's that found one
+//
+// The event loop is the header's definition operation for operation (float32, unfused, IEEE divide): every event time comes
+// from the current integer bound, never from an accumulated one.  The slab walk is box_walk.hpp's with a limit of one voxel: no
+// LDS, no private segment (the axes are unrolled, so every array index is a constant).  Records are written with plain stores.
+#include <hip/hip_runtime.h>
+
+#include "box_sweep.h"
+#include "box_walk.hpp"
+#include "vrc_launch.h"
+#include "vrc_params.h"
+
+namespace vrc {
+
+namespace {
+
+struct Sweep { float o[3], e[3], d[3]; bool rejected; };
+
+__device__ __forceinline__ Sweep load_sweep(const SweepParams &p, int64_t i) {
+    const float *s = p.box.boxes + 9 * i;
+    Sweep w;
+    w.rejected = false;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        w.o[a] = s[a];
+        const float m = s[3 + a];
+        w.d[a] = s[6 + a];
+        w.e[a] = w.o[a] + m;                                  // rounded to float32
+        const float od = w.o[a] + w.d[a], ed = w.e[a] + w.d[a];
+        w.rejected = w.rejected || !isfinite(w.o[a]) || !isfinite(m) || m < 0.0f || !(fabsf(w.o[a]) < 1073741824.0f) || !(fabsf(w.e[a]) < 1073741824.0f)
+                     || !isfinite(w.d[a]) || !(fabsf(od) < 1073741824.0f) || !(fabsf(ed) < 1073741824.0f);
+    }
+    return w;
+}
+
+// the shape of a sweep: a wave when the face of a moving axis can hold more than lane_face_max voxels
+__device__ __forceinline__ bool sweep_is_wave(const SweepParams &p, const Sweep &w) {
+    if (w.rejected) return false;
+    int64_t ext[3];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const int lo = (int)floorf(w.o[a]);
+        int hi = (int)ceilf(w.e[a]);
+        if (hi < lo + 1) hi = lo + 1;
+        const int64_t x = (int64_t)hi - lo + 1;               // (the range of a moving axis breathes by one layer)
+        ext[a] = x < p.box.map_dim[a] ? x : p.box.map_dim[a];
+    }
+    bool wave = false;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+        wave = wave || (w.d[a] != 0.0f && ext[(a + 1) % 3] * ext[(a + 2) % 3] > (int64_t)p.lane_face_max);
+    return wave;
+}
+
+// the first voxel a walk meets
+struct FirstSink {
+    int x, y, z, mat;
+    bool found;
+    __device__ __forceinline__ void operator()(int64_t, int vx, int vy, int vz, int m) { x = vx; y = vy; z = vz; mat = m; found = true; }
+};
+
+// The first counted voxel (Morton order) of the non-empty clipped range rg.  The range is tiled by aligned nodes of 2^s voxels
+// whose Morton order is the voxels'; a lane walks them one after the other, a wave takes 64 at a time (kWave: every lane of the
+// wave calls this with the same range).
+template <bool kWave>
+__device__ __forceinline__ bool slab_first(const BoxParams &q, const Range &rg, int lane, int &vx, int &vy, int &vz, int &mat) {
+    int L = 1;
+#pragma unroll
+    for (int x = 0; x < 3; x++) L = max(L, rg.hi[x] - rg.lo[x]);
+    const int sl = L <= 1 ? 0 : 32 - __clz(L - 1);            // ceil(log2 L)
+    int s = kWave ? sl - 3 : sl;                              // a wave: up to 9 x 9 nodes of a slab, one or two rounds of 64
+    if (s < 1) s = 1;
+    int a[3], b[3];
+    int64_t count = 1;
+#pragma unroll
+    for (int x = 0; x < 3; x++) {
+        a[x] = rg.lo[x] >> s; b[x] = ((rg.hi[x] - 1) >> s) + 1;
+        count *= (int64_t)(b[x] - a[x]);
+    }
+    for (int64_t j0 = 0; j0 < count; j0 += kWave ? 64 : 1) {
+        const int64_t j = j0 + (kWave ? lane : 0);
+        FirstSink sink = {0, 0, 0, 0, false};
+        if (j < count) {
+            int c[3];
+            morton_select(j, a, b, q.space_log2 - s, c);
+            Acc acc = {0, {0, 0, 0}, {0, 0, 0}};
+            walk<true>(q, c[0] << s, c[1] << s, c[2] << s, s, rg, acc, 0, 1, sink);
+        }
+        if (kWave) {
+            const unsigned long long mask = __ballot(sink.found);
+            if (mask) {
+                const int src = __ffsll(mask) - 1;            // the lowest lane = the first node in Morton order
+                vx = __shfl(sink.x, src, 64); vy = __shfl(sink.y, src, 64); vz = __shfl(sink.z, src, 64); mat = __shfl(sink.mat, src, 64);
+                return true;
+            }
+        } else if (sink.found) {
+            vx = sink.x; vy = sink.y; vz = sink.z; mat = sink.mat;
+            return true;
+        }
+    }
+    return false;
+}
+
+// One sweep, start to record.  kWave: all 64 lanes run this with the same sweep and lane 0 writes.
+template <bool kWave>
+__device__ __forceinline__ void sweep_run(const SweepParams &p, const Sweep &w, int64_t i, int lane) {
+    int flags = 0, normal = 0, vx = -1, vy = -1, vz = -1, mat = 0, events = 0;
+    float t = 0.0f;
+    if (w.rejected) {
+        flags = kSweepRejected;
+    } else {
+        int lo[3], hi[3], dim[3];
+        bool clipped = false;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            dim[a] = p.box.map_dim[a];
+            lo[a] = (int)floorf(w.o[a]);
+            hi[a] = (int)ceilf(w.e[a]);
+            if (hi[a] < lo[a] + 1) hi[a] = lo[a] + 1;
+            clipped = clipped || lo[a] < 0 || hi[a] > dim[a];
+        }
+        if (p.box.records[8 * i] & kBoxAny) {
+            const int32_t *v = p.box.voxels + 4 * i;
+            flags = kSweepStartSolid;
+            vx = v[0]; vy = v[1]; vz = v[2]; mat = v[3];
+        } else {
+            float t_last = 0.0f;
+            t = 1.0f;
+            while (true) {
+                bool left = false;
+#pragma unroll
+                for (int a = 0; a < 3; a++) left = left || (hi[a] <= 0 && w.d[a] <= 0.0f) || (lo[a] >= dim[a] && w.d[a] >= 0.0f);
+                if (left) { flags |= kSweepLeftMap; break; }
+                // the next event: trailing x y z, then leading x y z; the first strictly smallest time wins
+                float bt = 0.0f;
+                int code = -1;                                // axis | leading << 2
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    if (w.d[a] != 0.0f) {
+                        const float tt = w.d[a] > 0.0f ? ((float)(lo[a] + 1) - w.o[a]) / w.d[a] : (w.e[a] - (float)(hi[a] - 1)) / (-w.d[a]);
+                        if (code < 0 || tt < bt) { bt = tt; code = a; }
+                    }
+                }
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    if (w.d[a] != 0.0f) {
+                        const float tt = w.d[a] > 0.0f ? ((float)hi[a] - w.e[a]) / w.d[a] : (w.o[a] - (float)lo[a]) / (-w.d[a]);
+                        if (code < 0 || tt < bt) { bt = tt; code = 4 | a; }
+                    }
+                }
+                if (kWave) code = __builtin_amdgcn_readfirstlane(code);
+                if (code < 0 || !(bt < 1.0f)) break;          // free
+                if (events == p.cap) { flags |= kSweepEventCap; t = t_last; break; }
+                events++;
+                t_last = bt;
+                const int axis = code & 3;
+                if (!(code & 4)) {
+#pragma unroll
+                    for (int a = 0; a < 3; a++)
+                        if (a == axis) { if (w.d[a] > 0.0f) lo[a]++; else hi[a]--; }
+                } else {
+                    Range rg;
+                    bool empty = false, forward = false;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        if (a == axis) {
+                            forward = w.d[a] > 0.0f;
+                            const int layer = forward ? hi[a] : lo[a] - 1;
+                            rg.lo[a] = layer; rg.hi[a] = layer + 1;
+                            empty = empty || layer < 0 || layer >= dim[a];
+                        } else {
+                            rg.lo[a] = lo[a] > 0 ? lo[a] : 0;
+                            rg.hi[a] = hi[a] < dim[a] ? hi[a] : dim[a];
+                            empty = empty || rg.lo[a] >= rg.hi[a];
+                        }
+                    }
+                    if (!empty && slab_first<kWave>(p.box, rg, lane, vx, vy, vz, mat)) {
+                        flags |= kSweepHit;
+                        t = bt;
+                        normal = forward ? -(axis + 1) : axis + 1;
+                        break;
+                    }
+#pragma unroll
+                    for (int a = 0; a < 3; a++)
+                        if (a == axis) { if (forward) hi[a]++; else lo[a]--; }
+                }
+#pragma unroll
+                for (int a = 0; a < 3; a++) clipped = clipped || lo[a] < 0 || hi[a] > dim[a];
+            }
+        }
+        if (clipped) flags |= kSweepClipped;
+    }
+    if (!kWave || lane == 0) {
+        int32_t *rec = p.records + 8 * i;
+        rec[0] = flags; rec[1] = normal; rec[2] = __float_as_int(t);
+        rec[3] = vx; rec[4] = vy; rec[5] = vz; rec[6] = mat; rec[7] = events;
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kSweepThreads) void box_sweep_plan_kernel(const SweepParams p, int64_t *__restrict__ big_cnt) {
+    const int64_t stride = (int64_t)gridDim.x * kSweepThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kSweepThreads + threadIdx.x; i < p.box.n; i += stride)
+        big_cnt[i] = sweep_is_wave(p, load_sweep(p, i)) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kSweepThreads) void box_sweep_lane_kernel(const SweepParams p) {
+    const int64_t stride = (int64_t)gridDim.x * kSweepThreads;
+    for (int64_t i = (int64_t)blockIdx.x * kSweepThreads + threadIdx.x; i < p.box.n; i += stride) {
+        const Sweep w = load_sweep(p, i);
+        if (!sweep_is_wave(p, w)) sweep_run<false>(p, w, i, 0);
+    }
+}
+
+__global__ __launch_bounds__(kSweepThreads) void box_sweep_wave_kernel(const SweepParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wstride = (int64_t)gridDim.x * (kSweepThreads / 64);
+    const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64));
+    for (int64_t k = (int64_t)blockIdx.x * (kSweepThreads / 64) + wave_in_block; k < p.n_big; k += wstride) {
+        const int64_t i = owner(p.big_end, p.box.n, k);
+        sweep_run<true>(p, load_sweep(p, i), i, lane);
+    }
+}
+
+namespace {
+unsigned sweep_grid(int64_t threads) {
+    const int64_t blocks = (threads + kSweepThreads - 1) / kSweepThreads;
+    return (unsigned)(blocks < 1 ? 1 : (blocks < (1 << 20) ? blocks : (1 << 20)));   // (larger batches: the lanes loop)
+}
+}  // namespace
+
+hipError_t launch_sweep_plan(const SweepParams &p, int64_t *big_cnt, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(box_sweep_plan_kernel, dim3(sweep_grid(p.box.n)), dim3(kSweepThreads), 0, stream, p, big_cnt);
+    return hipGetLastError();
+}
+
+// the lane kernel over all sweeps, the wave kernel over the n_big sweeps the plan marked
+hipError_t launch_sweep(const SweepParams &p, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (p.n_big < p.box.n) hipLaunchKernelGGL(box_sweep_lane_kernel, dim3(sweep_grid(p.box.n)), dim3(kSweepThreads), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (p.n_big > 0) hipLaunchKernelGGL(box_sweep_wave_kernel, dim3(sweep_grid(p.n_big * 64)), dim3(kSweepThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+}  // namespace vrc

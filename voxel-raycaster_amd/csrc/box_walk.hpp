@@ -1,0 +1,196 @@
+// box_walk.hpp -- the stackless Morton-order walk of one aligned node restricted to a voxel range, shared by the box-overlap
+// queries (box_query.hip) and the swept-box queries (box_sweep.hip).  Device code only; each translation unit that includes
+// it gets its own copy (anonymous namespace).
+//
+// The walk (SVO branch) descends from the coarse table's cell (or the root) to the walk's node, then visits the node's subtree
+// in Morton order with a restart at every finished node -- stackless, so no LDS and no scratch.  Empty slots and slots outside
+// the range are skipped; a solid leaf (a valid leaf slot at any level, or any valid slot at the bottom level: query_locate's
+// rule, raycast_query.hip) is counted by volume; a solid cube that the range cuts is entered as a virtual node only to emit, so
+// its first k voxels in Morton order come without visiting the rest.  The array branch walks the same nodes over the map's
+// bytes.  Emitted voxels go to a sink, sink(entry, x, y, z, material): a list in memory (box queries) or registers (sweeps).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "box_query.h"
+#include "vrc_params.h"
+
+namespace vrc {
+
+namespace {
+
+// the packed cursor entry of raycast_query.hip's query_entry: bits 0-7 valid mask, 8-15 leaf mask, 16-63 index of the first kept child
+__device__ __forceinline__ uint64_t box_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
+    uint64_t base = index + (d & 0x7fffULL);
+    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
+    return (base << 16) | ((d >> 16) & 0xffffULL);
+}
+
+// length of [c, c + s) inside [lo, hi)
+__device__ __forceinline__ int overlap(int c, int s, int lo, int hi) {
+    const int a = c > lo ? c : lo, b = c + s < hi ? c + s : hi;
+    return b > a ? b - a : 0;
+}
+
+// coordinate `axis` of Morton index t (bit 3k + axis -> bit k)
+__device__ __forceinline__ int morton_coord(uint64_t t, int axis) {
+    int v = 0;
+    for (int k = 0; k < 21; k++) v |= (int)((t >> (3 * k + axis)) & 1ULL) << k;
+    return v;
+}
+
+struct Range { int lo[3], hi[3]; };
+struct Acc { int64_t count; int mn[3], mx[3]; };
+
+__device__ __forceinline__ bool counted(const BoxParams &q, int mat) {
+    return (q.flags & kBoxStoppingOnly) ? (mat == 5 || mat == 6) : mat != 0;
+}
+
+// the node of size 2^r at (cx, cy, cz) (r >= 1): 0 empty, 1 inside a solid leaf, 2 a descriptor (cur, its index)
+__device__ int region_descend(const BoxParams &q, int cx, int cy, int cz, int r, uint64_t &cur, uint64_t &cur_index) {
+    const int n = q.log2_dim;
+    int top;
+    cur_index = q.root_index;
+    if (q.coarse && r <= n - q.coarse_log2) {
+        const int csh = n - q.coarse_log2;
+        const uint64_t e = q.coarse[coarse_index((unsigned)(cx >> csh), (unsigned)(cy >> csh), (unsigned)(cz >> csh), q.coarse_log2)];
+        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
+        top = (int)(e >> kCoarseLevelShift);
+    } else {
+        cur = box_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
+        top = 0;
+    }
+    for (int guard = 0; guard <= n && n - top > r; guard++) {
+        const int b = n - top - 1;                        // (>= r >= 1: the child is never a single voxel)
+        const int i = ((cx >> b) & 1) | (((cy >> b) & 1) << 1) | (((cz >> b) & 1) << 2);
+        const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
+        if (!(masks & bit)) return 0;
+        if ((masks >> 8) & bit) return 1;
+        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
+        cur_index = (cur >> 16) + (uint64_t)rank;
+        cur = box_entry(q.descriptors, cur_index, q.descriptors[cur_index]);
+        top++;
+    }
+    return 2;
+}
+
+// kEmit = false: nothing is emitted
+struct NoSink {
+    __device__ __forceinline__ void operator()(int64_t, int, int, int, int) const {}
+};
+
+// Walk the node of size 2^r (r >= 1) at (cx, cy, cz) restricted to the range, in Morton order.  kEmit = false: count and
+// corners into acc.  kEmit = true: hand entry base + (voxels counted so far) to `sink` while it is below `limit`.
+template <bool kEmit, class Sink>
+__device__ void walk(const BoxParams &q, int cx, int cy, int cz, int r, const Range &rg, Acc &acc, int64_t base, int64_t limit,
+                     Sink &sink) {
+    uint64_t cur0 = 0, idx0 = 0;
+    const int state0 = q.svo ? region_descend(q, cx, cy, cz, r, cur0, idx0) : 2;
+    if (state0 == 0) return;
+    const uint64_t end = 1ULL << (3 * r);
+    uint64_t p = 0;
+    while (p < end) {
+        // descend from the walk's node toward p (a restart: the node that held p's predecessor is finished)
+        uint64_t cur = cur0, cur_index = idx0;
+        bool solid = state0 == 1;
+        int b = r, ox = cx, oy = cy, oz = cz;
+        while (true) {
+            const int cb = b - 1, s = 1 << cb;
+            const int i = (int)((p >> (3 * cb)) & 7ULL);
+            const int x0 = ox + (i & 1) * s, y0 = oy + ((i >> 1) & 1) * s, z0 = oz + ((i >> 2) & 1) * s;
+            const int wx = overlap(x0, s, rg.lo[0], rg.hi[0]), wy = overlap(y0, s, rg.lo[1], rg.hi[1]), wz = overlap(z0, s, rg.lo[2], rg.hi[2]);
+            if (wx && wy && wz) {
+                int kind = 0, mat = 5;                    // 0 empty, 1 solid, 2 a node to enter
+                uint64_t child = 0;
+                if (!q.svo) {
+                    if (cb > 0) {
+                        kind = 2;
+                    } else {
+                        // the frame's index (y stride map_dim[2]); past the array reads as empty (raycast_query.hip)
+                        const uint64_t idx = (uint64_t)((long)x0 + (long)q.map_dim[0] * ((long)y0 + (long)q.map_dim[2] * z0));
+                        mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
+                        kind = 1;
+                    }
+                } else if (solid) {
+                    kind = 1;
+                } else {
+                    const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
+                    if (masks & bit) {
+                        if (((masks >> 8) & bit) || cb == 0) {
+                            kind = 1;
+                            if (q.attach_lookup && cb == 0) {        // only bottom-level descriptors carry materials
+                                const uint64_t a = q.attachments[q.attach_lookup[cur_index]];
+                                mat = (int)(int8_t)(a >> (8 * i));
+                            }
+                        } else {
+                            kind = 2;
+                            child = (cur >> 16) + (uint64_t)((unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u);
+                        }
+                    }
+                }
+                const bool whole = wx == s && wy == s && wz == s;
+                if (kind == 1 && kEmit && !whole) kind = 3;    // a solid cube the box cuts: entered virtually, to emit in order
+                if (kind >= 2) {
+                    if (kind == 2 && q.svo) {
+                        cur = box_entry(q.descriptors, child, q.descriptors[child]);
+                        cur_index = child;
+                    }
+                    solid = solid || kind == 3;
+                    b = cb; ox = x0; oy = y0; oz = z0;
+                    continue;
+                }
+                if (kind == 1 && counted(q, mat)) {
+                    const int64_t vol = (int64_t)wx * wy * wz;
+                    if (kEmit) {
+                        // (whole: the cube lies in the box) its first voxels in Morton order
+                        const int64_t at = base + acc.count;
+                        const int64_t k = limit - at < vol ? limit - at : vol;
+                        for (int64_t t = 0; t < k; t++)
+                            sink(at + t, x0 + morton_coord((uint64_t)t, 0), y0 + morton_coord((uint64_t)t, 1), z0 + morton_coord((uint64_t)t, 2), mat);
+                        acc.count += vol;
+                        if (base + acc.count >= limit) return;
+                    } else {
+                        acc.count += vol;
+                        const int lx = x0 > rg.lo[0] ? x0 : rg.lo[0], ly = y0 > rg.lo[1] ? y0 : rg.lo[1], lz = z0 > rg.lo[2] ? z0 : rg.lo[2];
+                        acc.mn[0] = min(acc.mn[0], lx); acc.mn[1] = min(acc.mn[1], ly); acc.mn[2] = min(acc.mn[2], lz);
+                        acc.mx[0] = max(acc.mx[0], lx + wx - 1); acc.mx[1] = max(acc.mx[1], ly + wy - 1); acc.mx[2] = max(acc.mx[2], lz + wz - 1);
+                    }
+                }
+            }
+            // the child is done: on to its next sibling, or (the last child) restart toward the next node
+            p = ((p >> (3 * cb)) + 1ULL) << (3 * cb);
+            if (i == 7) break;
+        }
+    }
+}
+
+// first box whose inclusive end is above item k
+__device__ int64_t owner(const int64_t *__restrict__ end, int64_t n, int64_t k) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (end[mid] > k) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// the j-th node (Morton order) of the node range [a, b) per axis, in a grid of 2^m nodes per axis
+__device__ void morton_select(int64_t j, const int a[3], const int b[3], int m, int c[3]) {
+    c[0] = c[1] = c[2] = 0;
+    for (int l = m - 1; l >= 0; l--) {
+        const int h = 1 << l;
+        int nx = c[0], ny = c[1], nz = c[2];
+        for (int o = 0; o < 8; o++) {
+            const int x0 = c[0] + (o & 1) * h, y0 = c[1] + ((o >> 1) & 1) * h, z0 = c[2] + ((o >> 2) & 1) * h;
+            const int64_t k = (int64_t)overlap(x0, h, a[0], b[0]) * overlap(y0, h, a[1], b[1]) * overlap(z0, h, a[2], b[2]);
+            nx = x0; ny = y0; nz = z0;
+            if (j < k) break;
+            j -= k;
+        }
+        c[0] = nx; c[1] = ny; c[2] = nz;
+    }
+}
+
+}  // namespace
+
+}  // namespace vrc

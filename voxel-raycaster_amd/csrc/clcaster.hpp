@@ -144,6 +144,14 @@ public:
         return ok(vrc_last_kernel(h_, rank, &info));
     }
 
+    // extension: Map::ShortRayIntersection (Map.h:53, a stub in the reference) as a batch -- how far each box moves before it
+    // touches a counted voxel (vrc_sweep_boxes): sweeps = 9 floats each (origin, extent, displacement), records = 8 int32 each
+    bool sweep_boxes(const std::vector<float> &sweeps, std::vector<int32_t> &records, int32_t max_events = 0, bool stopping_only = false) {
+        const int64_t n = (int64_t)(sweeps.size() / 9);
+        records.resize((size_t)8 * n);
+        return ok(vrc_sweep_boxes(h_, sweeps.data(), n, max_events, stopping_only ? VRC_SWEEP_STOPPING_ONLY : 0u, records.data()));
+    }
+
     int last_status() const { return status_; }
     std::string last_error() const { return h_ ? vrc_last_error(h_) : "not initialised"; }
     vrc_caster *handle() { return h_; }

@@ -25,6 +25,7 @@
 
 #include "../../include/vrc.h"
 #include "box_query.h"
+#include "box_sweep.h"
 #include "raycast_query.h"
 #include "vrc_launch.h"
 #include "vrc_params.h"
@@ -130,6 +131,11 @@ struct vrc_caster {
     void *d_box_plan = nullptr; int64_t *d_box_scan = nullptr; int32_t *d_box_corner = nullptr; int64_t box_capacity = 0;
     int64_t *d_box_items = nullptr; int64_t box_item_capacity = 0;
     void *d_box_temp = nullptr; size_t box_temp_bytes = 0;
+    // vrc_sweep_boxes: staging of the host call (sweeps, records); the start test's records, counts and first voxels, the
+    // shape flags and their scan; the number of wave-shaped sweeps (read back with the start test's item totals)
+    float *d_sweep_in = nullptr; int32_t *d_sweep_out = nullptr; int64_t sweep_io_capacity = 0;
+    int32_t *d_sweep_rec = nullptr, *d_sweep_vox = nullptr; int64_t *d_sweep_cnt = nullptr, *d_sweep_scan = nullptr; int64_t sweep_capacity = 0;
+    int64_t sweep_n_big = 0;
 
     // live (retained) host pointers
     const float *cam_dir = nullptr, *cam_pos = nullptr;
@@ -193,9 +199,10 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
         }                                                                                         \
     } while (0)
 
-// vrc_cast_rays' and vrc_box_intersection's staging and scratch buffers (the caller's device is left as it was)
+// vrc_cast_rays', vrc_box_intersection's and vrc_sweep_boxes' staging and scratch buffers (the caller's device is left as it was)
 void release_query_staging(vrc_caster *h) {
-    if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp) return;
+    if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp &&
+        !h->d_sweep_in && !h->d_sweep_rec) return;
     {
         DeviceRestore restore;
         (void)hipSetDevice(h->device);
@@ -204,6 +211,8 @@ void release_query_staging(vrc_caster *h) {
         release(h->d_box_in); release(h->d_box_rec); release(h->d_box_cnt); release(h->d_box_vox);
         release(h->d_box_plan); release(h->d_box_scan); release(h->d_box_corner); release(h->d_box_items); release(h->d_box_temp);
         h->box_io_capacity = 0; h->box_vox_bytes = 0; h->box_capacity = 0; h->box_item_capacity = 0; h->box_temp_bytes = 0;
+        release(h->d_sweep_in); release(h->d_sweep_out); release(h->d_sweep_rec); release(h->d_sweep_vox); release(h->d_sweep_cnt); release(h->d_sweep_scan);
+        h->sweep_io_capacity = 0; h->sweep_capacity = 0;
     }
     (void)hipGetLastError();
 }
@@ -1808,17 +1817,12 @@ int box_check(vrc_caster *h, const void *boxes, int64_t n, int32_t max_voxels, u
     return query_check(h, boxes, n, 0, 0, records, what);
 }
 
-// Plan, scans, count, (scan, emit), finalize on the handle's stream (current device: h->device).  The tree's guard is held
-// throughout, as query_enqueue holds it; the coarse table is used when vrc_prepare / validate / a frame has built it for this
-// tree, never built here.  One host wait in the middle: the item totals size the grid and the per-item scratch.
-int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags, int32_t *d_rec, int64_t *d_cnt,
-                int32_t *d_vox) {
-    std::unique_lock<std::mutex> lock(h->tree->guard);
-    vrc::BoxParams q;
-    memset(&q, 0, sizeof(q));
-    q.boxes = d_boxes; q.n = n; q.max_voxels = max_voxels; q.flags = flags;
-    q.records = d_rec; q.counts = d_cnt; q.voxels = max_voxels > 0 ? d_vox : nullptr;
-    bind_scene(h, h->tree.get(), q);
+// Plan, scans, count, (scan, emit), finalize on the handle's stream (current device: h->device) for the boxes, outputs and
+// scene q names; the scratch fields of q are filled in here.  The caller holds the tree's guard.  One host wait in the middle:
+// the item totals size the grid and the per-item scratch.
+int box_passes(vrc_caster *h, vrc::BoxParams &q) {
+    const int64_t n = q.n;
+    const int32_t max_voxels = q.max_voxels;
     // the aligned space the items tile: the tree's, or the map's largest side rounded up
     const int32_t side = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
     q.space_log2 = 1;
@@ -1863,6 +1867,19 @@ int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxe
     return VRC_OK;
 }
 
+// The tree's guard is held throughout, as query_enqueue holds it; the coarse table is used when vrc_prepare / validate / a
+// frame has built it for this tree, never built here.
+int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxels, uint32_t flags, int32_t *d_rec, int64_t *d_cnt,
+                int32_t *d_vox) {
+    std::unique_lock<std::mutex> lock(h->tree->guard);
+    vrc::BoxParams q;
+    memset(&q, 0, sizeof(q));
+    q.boxes = d_boxes; q.box_stride = 6; q.n = n; q.max_voxels = max_voxels; q.flags = flags;
+    q.records = d_rec; q.counts = d_cnt; q.voxels = max_voxels > 0 ? d_vox : nullptr;
+    bind_scene(h, h->tree.get(), q);
+    return box_passes(h, q);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1904,6 +1921,90 @@ int vrc_box_intersection_device(vrc_caster *h, const void *d_boxes, int64_t n, i
     VRC_TRY(wait_for_null_stream(h));
     VRC_TRY(box_enqueue(h, static_cast<const float *>(d_boxes), n, max_voxels, flags, static_cast<int32_t *>(d_records),
                         static_cast<int64_t *>(d_counts), static_cast<int32_t *>(d_voxels)));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// batched swept-box queries (vrc_sweep_boxes / vrc_sweep_boxes_device, box_sweep.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the argument checks of both calls, then the readiness checks of the ray queries; nothing is launched when one fails
+int sweep_check(vrc_caster *h, const void *sweeps, int64_t n, int32_t max_events, uint32_t flags, const void *records, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    if (max_events < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: max_events = %d < 0", what, (int)max_events);
+    if (flags & ~(uint32_t)VRC_SWEEP_STOPPING_ONLY)
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_SWEEP_STOPPING_ONLY));
+    if (n > 0 && (!sweeps || !records)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null sweeps or records", what);
+    return query_check(h, sweeps, n, 0, 0, records, what);
+}
+
+// The shape flags and their scan, the start test (the box query's passes over the start boxes, a list of one voxel, into the
+// handle's scratch), then the sweep kernels, on the handle's stream (current device: h->device).  The tree's guard is held
+// throughout and nothing derived is built, as for a box query.  The one host wait is the start test's.
+int sweep_enqueue(vrc_caster *h, const float *d_sweeps, int64_t n, int32_t max_events, uint32_t flags, int32_t *d_rec) {
+    std::unique_lock<std::mutex> lock(h->tree->guard);
+    VRC_TRY(grow(h, h->sweep_capacity, n, {{h->d_sweep_rec, sizeof(int32_t) * 8 * (size_t)n}, {h->d_sweep_vox, sizeof(int32_t) * 4 * (size_t)n},
+                                           {h->d_sweep_cnt, sizeof(int64_t) * (size_t)n}, {h->d_sweep_scan, sizeof(int64_t) * 2 * (size_t)n}}));
+    vrc::SweepParams p;
+    memset(&p, 0, sizeof(p));
+    vrc::BoxParams &q = p.box;
+    q.boxes = d_sweeps; q.box_stride = 9; q.n = n; q.max_voxels = 1;
+    q.flags = (flags & VRC_SWEEP_STOPPING_ONLY) ? vrc::kBoxStoppingOnly : 0u;
+    q.records = h->d_sweep_rec; q.counts = h->d_sweep_cnt; q.voxels = h->d_sweep_vox;
+    bind_scene(h, h->tree.get(), q);
+    p.records = d_rec;
+    const int64_t dims = (int64_t)q.map_dim[0] + q.map_dim[1] + q.map_dim[2];
+    p.cap = max_events > 0 ? max_events : (int32_t)std::min<int64_t>(INT32_MAX, 2 * dims + 64);
+    p.lane_face_max = (int32_t)std::max<int64_t>(0, std::min<int64_t>(INT32_MAX, setting_or(h, "sweep_lane_face", vrc::kSweepLaneFaceMax)));
+    int64_t *big_cnt = h->d_sweep_scan, *big_end = h->d_sweep_scan + n;
+    p.big_end = big_end;
+    size_t need = 0;
+    HIP_TRY(h, vrc::box_scan(nullptr, &need, big_cnt, big_end, n, h->stream));
+    VRC_TRY(grow(h, h->box_temp_bytes, need, {{h->d_box_temp, need}}));
+    HIP_TRY(h, vrc::launch_sweep_plan(p, big_cnt, h->stream));
+    size_t bytes = h->box_temp_bytes;
+    HIP_TRY(h, vrc::box_scan(h->d_box_temp, &bytes, big_cnt, big_end, n, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&h->sweep_n_big, big_end + n - 1, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    VRC_TRY(box_passes(h, q));                                     // (waits for the stream: sweep_n_big has arrived)
+    p.n_big = h->sweep_n_big;
+    HIP_TRY(h, vrc::launch_sweep(p, h->stream));
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_sweep_boxes(vrc_caster *h, const float *sweeps, int64_t n, int32_t max_events, uint32_t flags, int32_t *records) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = sweep_check(h, sweeps, n, max_events, flags, records, "sweep_boxes");
+    if (rc != VRC_OK || n == 0) return rc;
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    VRC_TRY(grow(h, h->sweep_io_capacity, n, {{h->d_sweep_in, sizeof(float) * 9 * (size_t)n}, {h->d_sweep_out, sizeof(int32_t) * 8 * (size_t)n}}));
+    HIP_TRY(h, hipMemcpyAsync(h->d_sweep_in, sweeps, sizeof(float) * 9 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    VRC_TRY(sweep_enqueue(h, h->d_sweep_in, n, max_events, flags, h->d_sweep_out));
+    HIP_TRY(h, hipMemcpyAsync(records, h->d_sweep_out, sizeof(int32_t) * 8 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+int vrc_sweep_boxes_device(vrc_caster *h, const void *d_sweeps, int64_t n, int32_t max_events, uint32_t flags, void *d_records) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = sweep_check(h, d_sweeps, n, max_events, flags, d_records, "sweep_boxes_device");
+    if (rc != VRC_OK || n == 0) return rc;
+    if (((uintptr_t)d_sweeps & 3u) || ((uintptr_t)d_records & 3u))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "sweep_boxes_device: sweeps and records must be 4-byte aligned");
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!query_pointer_ok(h, d_sweeps) || !query_pointer_ok(h, d_records))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "sweep_boxes_device: sweeps and records must be memory the GPU of the handle (device %d) can read and write", h->device);
+    VRC_TRY(wait_for_null_stream(h));
+    VRC_TRY(sweep_enqueue(h, static_cast<const float *>(d_sweeps), n, max_events, flags, static_cast<int32_t *>(d_records)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return VRC_OK;
 }

@@ -17,6 +17,7 @@ struct RaycastParams;
 struct LaunchRecord;
 struct QueryParams;
 struct BoxParams;
+struct SweepParams;
 
 // raycast_kernel.hip
 hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
@@ -54,6 +55,10 @@ hipError_t launch_box_plan(const BoxParams &q, int64_t *small_cnt, int64_t *big_
 hipError_t launch_box_count(const BoxParams &q, int pass, hipStream_t stream);
 hipError_t launch_box_finalize(const BoxParams &q, hipStream_t stream);
 hipError_t box_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *out, int64_t n, hipStream_t stream);
+
+// box_sweep.hip
+hipError_t launch_sweep_plan(const SweepParams &p, int64_t *big_cnt, hipStream_t stream);
+hipError_t launch_sweep(const SweepParams &p, hipStream_t stream);
 
 // svo_builder_gpu.hip
 int build_shell_terrain_device(hipStream_t stream, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
