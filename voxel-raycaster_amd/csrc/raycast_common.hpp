@@ -326,9 +326,36 @@ __device__ __forceinline__ void ray_finish(Ray &r, const RaycastParams &p, unsig
 // the row count is a multiple of 8 and otherwise keeps the row-major order (XCD k gets every 8th block of each row);
 // either way every XCD renders the same sky/ground mix.  xcd_mode 0 gives XCD k the k-th contiguous eighth of the
 // image (L2 locality, but 37 % slower: sky rows take longer than ground rows); xcd_mode 2 never remaps.
-__device__ __forceinline__ void block_pixel(const RaycastParams &p, int &px, int &py, int &buffer_row) {
-    const int nblocks = gridDim.x;
-    int bid = blockIdx.x;
+// kTiles: tiles (waves) per workgroup.  The map above is stated for GROUPS of kTilesPerBlock tiles (32 x 8 pixels); a kernel
+// whose workgroup is a whole group (kTiles == kTilesPerBlock: mode B, the array kernel) has group = blockIdx.x.  A kernel with
+// finer workgroups (the exact SVO kernel) launches S = kTilesPerBlock / kTiles workgroups per group, dealt so that a group
+// stays on the XCD it had and an XCD meets its groups in the order it did: workgroup w is sub-block (w / 8) % S of group
+// (w / 8S) * 8 + w % 8 -- the S workgroups of group g are w = g % 8 + 8 * (S * (g / 8) + sub), all congruent to g mod 8.  The
+// launch rounds the group count up to a multiple of 8 (svo_workgroups()); a workgroup whose group does not exist returns false
+// and renders nothing.
+template <int kTiles>
+__device__ __forceinline__ bool workgroup_group(const RaycastParams &p, int &nblocks, int &bid, int &sub) {
+    static_assert(kTiles >= 1 && kTilesPerBlock % kTiles == 0, "a workgroup is a whole fraction of a 4-tile group");
+    constexpr int S = kTilesPerBlock / kTiles;
+    nblocks = gridDim.x; bid = blockIdx.x; sub = 0;
+    if (S > 1) {
+        nblocks = p.blocks_x * p.local_tile_rows;
+        const int w = blockIdx.x;
+        bid = (w / (8 * S)) * 8 + (w & 7);
+        sub = (w >> 3) % S;
+    }
+    return bid < nblocks;
+}
+// (false, and nothing set: the workgroup's group does not exist -- the kernel asks workgroup_exists() first, before it takes anything)
+template <int kTiles>
+__device__ __forceinline__ bool workgroup_exists(const RaycastParams &p) {
+    int nblocks, bid, sub;
+    return workgroup_group<kTiles>(p, nblocks, bid, sub);
+}
+template <int kTiles = kTilesPerBlock>
+__device__ __forceinline__ bool block_pixel(const RaycastParams &p, int &px, int &py, int &buffer_row) {
+    int nblocks, bid, sub;
+    if (!workgroup_group<kTiles>(p, nblocks, bid, sub)) return false;
     const int per_xcd = nblocks >> 3;
     int local_ty, bx;
     if (p.xcd_mode == 1 && per_xcd > 0 && bid < (per_xcd << 3) && (p.local_tile_rows & 7) == 0) {
@@ -344,11 +371,12 @@ __device__ __forceinline__ void block_pixel(const RaycastParams &p, int &px, int
     }
     const int band = local_ty / p.band_tiles;
     const int tile_y = (band * p.tile_world + p.tile_rank) * p.band_tiles + (local_ty - band * p.band_tiles);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = sub * kTiles + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     px = (bx * kTilesPerBlock + wave) * kTileW + (lane & (kTileW - 1));
     py = tile_y * kTileH + lane / kTileW;
     // row of this pixel in the viewport / image / hit buffers: the image row, or its position among this rank's rows
     buffer_row = p.row_sliced ? local_ty * kTileH + lane / kTileW : py;
+    return true;
 }
 
 // Values the COLD code needs (hit block, epilogue) and the step loop does not: computed where they are used, behind an empty
@@ -378,19 +406,31 @@ __device__ __forceinline__ long cold_pixel_index(const RaycastParams &p, long pi
     return pix0 + (long)((lane & (kTileW - 1)) + p.width * (lane / kTileW));
 }
 
-// per-block counter partials (no global atomics): wave shuffle reduce, LDS, one row per block
+// per-block counter partials (no global atomics): wave shuffle reduce, LDS, one row per block.
+// kTiles == 1 (a workgroup of one wave): the row is built in registers -- after the butterfly every lane holds the seven sums, lane k
+// keeps sum k, lane kCtrWatchdog the wave's `watchdog` (wave-uniform) -- and written without a barrier or LDS; kCtrLds (profiling
+// builds): plus what this same wave added to block_ctr earlier in program order
+template <int kTiles = kTilesPerBlock, bool kCtrLds = true>
 __device__ __forceinline__ void publish_counters(const RaycastParams &p, unsigned long long *block_ctr,
-                                                 const unsigned (&vals)[7], int thread) {
+                                                 const unsigned (&vals)[7], int thread, bool watchdog = false) {
     const int lane = thread & 63;
+    unsigned long long row = 0;
 #pragma unroll
     for (int k = 0; k < 7; k++) {
         unsigned long long v = vals[k];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0 && v) atomicAdd(&block_ctr[k], v);
+        if constexpr (kTiles == 1) { if (lane == k) row = v; }
+        else if (lane == 0 && v) atomicAdd(&block_ctr[k], v);
     }
-    __syncthreads();
-    if (thread < kCtrCount) p.counters[(long)blockIdx.x * kCtrCount + thread] = block_ctr[thread];
+    if constexpr (kTiles == 1) {
+        if (lane == kCtrWatchdog && watchdog) row = 1;
+        if constexpr (kCtrLds) { if (lane < kCtrCount) row += block_ctr[lane]; }
+        if (lane < kCtrCount) p.counters[(long)blockIdx.x * kCtrCount + lane] = row;
+    } else {
+        __syncthreads();
+        if (thread < kCtrCount) p.counters[(long)blockIdx.x * kCtrCount + thread] = block_ctr[thread];
+    }
 }
 
 }  // namespace vrc

@@ -28,8 +28,10 @@
 //     stretch by closed forms that reproduce the float recurrence and the
 //     iteration count bit for bit.
 //   * One wavefront = one 8x8 pixel tile (coherent rays walk the same nodes and
-//     L1/L2 lines), 4 tiles per 256-thread block; blocks go to the XCDs round-robin and the block -> tiles
-//     mapping (block_pixel) gives every XCD the same sky/ground mix.
+//     L1/L2 lines).  Groups of 4 adjacent tiles go to the XCDs round-robin and the group -> tiles mapping
+//     (block_pixel) gives every XCD the same sky/ground mix; the array kernel and mode B run a group as one
+//     256-thread block, the SVO kernel here as four single-wave workgroups on the group's XCD, so that a
+//     finished tile gives its wave slot, registers and LDS back at once (vrc_params.h).
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -133,6 +135,10 @@ __device__ unsigned long long g_jump_stats[12];   // [8], [9]: wave-iterations a
 // profiling build only: shader-clock ticks (s_memtime) a wave spends per phase of a round, summed over waves
 //   [0] jump estimate + vote  [1] wave-wide Euclid fill  [2] jump block  [3] safe run  [4] single step + exact loop
 //   [5] node events  [6] relight + hit block  [7] set-up and epilogue  [8] whole kernel
+// ... and per WORKGROUP, by whether one of its rays cast a shadow ray (9.. none did / 12.. some did): [9] / [12] the sum of its
+// waves' lives, [10] / [13] waves x the longest of them -- the wave-slot time the workgroup holds, since slots, registers and LDS go
+// back when its last wave ends -- [11] / [14] workgroups.  1 - [9] / [10]: the share of that time a finished wave's slot sits idle
+// (tools/block_imbalance.py; build with -DVRC_SVO_TILES=4 for the figure of 4-tile workgroups)
 __device__ unsigned long long g_time_stats[16];
 #define VRC_TICK(slot) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if ((tid & 63) == 0) t_acc[slot] += now_ - t_last; t_last = now_; } while (0)
 #else
@@ -169,11 +175,19 @@ constexpr int kHwRegXccId = (3 << 11) | (0 << 6) | 20;
 //         the descriptor-read counter now counts the reads this traversal makes, not SURVEY 8d's canonical ones (setting
 //         empty_boxes = 0 renders with the canonical counter).  The cursor keeps the INDEX of the descriptor whose masks it holds
 //         in a second LDS array beside the stack ([level - lc][thread], one dword).
-template <bool kJump, bool kMulti, bool kTuned, int kLdsRows = 0, bool kCoarse = false, bool kBox = false>
 #ifndef VRC_MIN_BLOCKS_JUMP_MULTI
 #define VRC_MIN_BLOCKS_JUMP_MULTI VRC_MIN_BLOCKS_JUMP
 #endif
-__global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUMP_MULTI : VRC_MIN_BLOCKS_JUMP) : VRC_MIN_BLOCKS) void raycast_svo_kernel(const RaycastParams p) {
+// The budgets are stated in WAVES, so that the registers an instance may use do not move with the workgroup size: 5 waves per SIMD
+// (20 per CU, 96 VGPRs) for the jump instances, 6 (24 per CU, 80 VGPRs) for the plain ones.  The second argument of
+// __launch_bounds__ is waves per SIMD (hipcc: amdgpu_waves_per_eu) -- with 256-thread blocks on four SIMDs that is also the blocks
+// per CU, which is how the VRC_MIN_BLOCKS* knobs came by their names -- and the workgroups a CU must hold for it follow from the
+// tiles of a workgroup (the occupancy question of jump_tables_lds_rows)
+constexpr int svo_waves_per_simd(bool jump, bool multi) { return jump ? (multi ? VRC_MIN_BLOCKS_JUMP_MULTI : VRC_MIN_BLOCKS_JUMP) : VRC_MIN_BLOCKS; }
+constexpr int svo_min_workgroups(bool jump, bool multi) { return svo_waves_per_simd(jump, multi) * 4 / svo_tiles_per_workgroup(jump, multi); }
+template <bool kJump, bool kMulti, bool kTuned, int kLdsRows = 0, bool kCoarse = false, bool kBox = false>
+__global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_waves_per_simd(kJump, kMulti)) void raycast_svo_kernel(const RaycastParams p) {
+    constexpr int kWgTiles = svo_tiles_per_workgroup(kJump, kMulti), kWgThreads = 64 * kWgTiles;   // this kernel's workgroup: NOT kBlockThreads
     // kLdsRows: rows of the Euclid-table ring in LDS (kLdsTab), 0 = the tables live in global memory (ring of 4).  3 rows x 3 pairs x
     // 8 bytes = 72 bytes per lane beside a stack of up to 4 levels with the boxes' index array (6 without) inside the 128 bytes a lane
     // has at 5 blocks per CU; 2 rows = 48 bytes for the deeper stacks of trees from depth 15 on WITH boxes (5 - 6 levels x 12 bytes) --
@@ -189,10 +203,26 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
     __shared__ int s_jump_slot;
     const int tid = threadIdx.x;
     const int wave_in_block = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar: the epilogue rebuilds the thread index from it)
-    if (tid < kCtrCount) block_ctr[tid] = 0;
-    if (kLdsTab) {
-        if (tid == 0) s_jump_slot = 0;
-    } else if (kJump && tid == 0) {
+    // the launch rounds the group count up to a multiple of 8 (block_pixel): a workgroup of a group that does not exist leaves a
+    // zero counter row and ends here -- the whole workgroup, before it has taken a table slot or met a barrier
+    if (!workgroup_exists<kWgTiles>(p)) {
+        if (tid < kCtrCount) p.counters[(long)blockIdx.x * kCtrCount + tid] = 0;
+        return;
+    }
+    // A single-wave workgroup keeps its counters in registers (publish_counters) and an instance with the tables in LDS takes no slot:
+    // neither of the two static variables is then referenced, and none is allocated.  That matters: 20 workgroups of 64 lanes x 120
+    // bytes (4 levels with the boxes + 3 table rows) fill the CU's 160 KB to the byte, as 5 blocks of 256 lanes did not quite.
+#ifdef VRC_SCHED_STATS
+    constexpr bool kCtrLds = true;                        // (profiling build: the scheduler statistics are LDS atomics)
+#else
+    constexpr bool kCtrLds = kWgTiles > 1;
+#endif
+    if constexpr (kCtrLds) { if (tid < kCtrCount) block_ctr[tid] = 0; }
+#ifdef VRC_TIME_STATS
+    __shared__ unsigned long long s_life[3];              // sum and maximum of the waves' lives, "a shadow ray was cast"
+    if (tid < 3) s_life[tid] = 0;
+#endif
+    if (kJump && !kLdsTab && tid == 0) {
         // the block's slot in the table buffer: tables exist for RESIDENT blocks only (they stay in the L2 / MALL), so a
         // block takes a free slot when it starts and gives it back at its end.  The slots are divided among the XCDs and a
         // block only ever takes one of the XCD it RUNS on (HW_REG_XCC_ID, not a guess from blockIdx): an XCD's L2 is not
@@ -217,7 +247,7 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
     __syncthreads();
 
     int px, py, brow;
-    block_pixel(p, px, py, brow);
+    block_pixel<kWgTiles>(p, px, py, brow);
     const bool in_image = px < p.width && py < p.height;
     const long pix = (long)px + (long)p.width * brow;
 
@@ -252,7 +282,7 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
     const int lc = kCoarse ? p.coarse_log2 : 0, csh = n - lc;           // table level, log2 of its cell size
     const int sbase = kCoarse ? lc : 1;                   // level of stack slot 0
     // kBox: the descriptor index of every stack level, behind the stack; boxw = the box word of the empty node locate() found
-    uint32_t *const lds_own = reinterpret_cast<uint32_t *>(lds_stack + (size_t)(kCoarse ? n - lc : (n > 1 ? n - 1 : 1)) * kBlockThreads);
+    uint32_t *const lds_own = reinterpret_cast<uint32_t *>(lds_stack + (size_t)(kCoarse ? n - lc : (n > 1 ? n - 1 : 1)) * kWgThreads);
     uint32_t boxw = 0;
     // the empty child i of a node with valid mask `valid`, widened over the empty siblings that lie ahead of the ray (enter_node's
     // rule for the box-less instances), as a box word: extent code 1 -- one node size -- on the side the ray leaves through
@@ -293,8 +323,8 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
             if (top > 0 && (diff >> (n - top)) != 0) top = n - (31 - __clz((int)diff)) - 1;   // deepest level whose node holds both voxels
             // (the entry comes from the stack also when nothing is popped: one ds_read_b64 per event instead of two registers
             // carried through the round loop -- every level from sbase down to `top` was stored on the way down)
-            cur = (!kCoarse && top == 0) ? root_entry : lds_stack[(top - sbase) * kBlockThreads + tid];
-            if (kBox) own = lds_own[(top - sbase) * kBlockThreads + tid];   // (top >= lc here: a cursor above the table's level always takes the table)
+            cur = (!kCoarse && top == 0) ? root_entry : lds_stack[(top - sbase) * kWgThreads + tid];
+            if (kBox) own = lds_own[(top - sbase) * kWgThreads + tid];   // (top >= lc here: a cursor above the table's level always takes the table)
         }
         pvx = x; pvy = y; pvz = z;
         for (;;) {
@@ -320,8 +350,8 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
             if (kBox) own = p.box_child ? (top + 1 < p.box_levels ? p.box_child[own] + rank : 0u) : (uint32_t)child;
             c_desc++;
             cur = make_entry(descriptors, child, d);
-            lds_stack[(top + 1 - sbase) * kBlockThreads + tid] = cur;   // level top+1 (>= lc + 1 with the table)
-            if (kBox) lds_own[(top + 1 - sbase) * kBlockThreads + tid] = own;
+            lds_stack[(top + 1 - sbase) * kWgThreads + tid] = cur;   // level top+1 (>= lc + 1 with the table)
+            if (kBox) lds_own[(top + 1 - sbase) * kWgThreads + tid] = own;
             top++;
         }
     };
@@ -330,7 +360,7 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
         if (!p.attach_lookup || top != n - 1) return 5;   // only bottom-level descriptors carry materials
         uint64_t node = p.root_index;
         if (top > 0) {
-            const uint64_t parent = (!kCoarse && top == 1) ? root_entry : lds_stack[(top - 1 - sbase) * kBlockThreads + tid];
+            const uint64_t parent = (!kCoarse && top == 1) ? root_entry : lds_stack[(top - 1 - sbase) * kWgThreads + tid];
             const int slot = ((x >> 1) & 1) | (((y >> 1) & 1) << 1) | (((z >> 1) & 1) << 2);
             node = (parent >> 16) + (uint64_t)(__popc((unsigned)parent & 0xffu & ((2u << slot) - 1u)) - 1);
         }
@@ -408,9 +438,9 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
     uint32_t jrows = 0;
     // rows in LDS: behind the traversal stack, [ring row][pair][thread], one 8-byte word each (ds_read_b64 / ds_write_b64, consecutive threads)
     constexpr int kRing = kLdsTab ? kLdsRows : 4;        // table rows per ray (exact_jump.hpp)
-    const int jstride = kLdsTab ? kBlockThreads : 64;
-    if (kLdsTab) jtab = reinterpret_cast<JumpWord *>(lds_own + (kBox ? (size_t)(n - lc) * kBlockThreads : 0)) + tid;   // (8-byte aligned: whole multiples of 1 KB before it)
-    else if (kJump && s_jump_slot >= 0) jtab = reinterpret_cast<JumpWord *>(p.jump_cache) + ((size_t)s_jump_slot * kTilesPerBlock + (tid >> 6)) * (size_t)(3 * kRing * 64) + (tid & 63);
+    const int jstride = kLdsTab ? kWgThreads : 64;
+    if (kLdsTab) jtab = reinterpret_cast<JumpWord *>(lds_own + (kBox ? (size_t)(n - lc) * kWgThreads : 0)) + tid;   // (8-byte aligned: whole multiples of 1 KB before it)
+    else if (kJump && s_jump_slot >= 0) jtab = reinterpret_cast<JumpWord *>(p.jump_cache) + ((size_t)s_jump_slot * kWgTiles + (tid >> 6)) * (size_t)(3 * kRing * 64) + (tid & 63);
 
     if (in_image) {
         if (!ray_setup(r, p, pix)) {
@@ -858,7 +888,7 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
 
     const int tid_end = cold_thread_index(wave_in_block);  // threadIdx.x, without a register through the round loop
     if (rounds_left < 0 && (tid_end & 63) == 0) {
-        atomicAdd(&block_ctr[kCtrWatchdog], 1ULL);
+        if constexpr (kWgTiles > 1) atomicAdd(&block_ctr[kCtrWatchdog], 1ULL);   // (one wave: publish_counters takes it as an argument)
         if (p.watchdog_flag) __hip_atomic_store(p.watchdog_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     unsigned c_steps = 0, c_tex = 0, c_shadow = 0, c_primary = 0, c_unwritten = 0;
@@ -890,12 +920,24 @@ __global__ __launch_bounds__(kBlockThreads, kJump ? (kMulti ? VRC_MIN_BLOCKS_JUM
         if ((tid_end & 63) == 0) {
             t_acc[8] = now_ - t_begin;
             for (int k = 0; k < 9; k++) atomicAdd(&g_time_stats[k], t_acc[k]);
+            atomicAdd(&s_life[0], t_acc[8]);
+            atomicMax(&s_life[1], t_acc[8]);
         }
+        if (__ballot(c_shadow != 0) != 0 && (tid_end & 63) == 0) atomicOr(&s_life[2], 1ULL);
     }
 #endif
     const unsigned vals[7] = {c_primary, c_shadow, c_desc, c_tex, 0u, c_steps, c_unwritten};
-    publish_counters(p, block_ctr, vals, tid_end);        // (a __syncthreads inside: every wave of the block is through with its tables)
+    publish_counters<kWgTiles, kCtrLds>(p, block_ctr, vals, tid_end, rounds_left < 0);   // (several waves: a __syncthreads inside, every wave of the workgroup is through with its tables)
     if (kJump && !kLdsTab && tid_end == 0 && s_jump_slot >= 0) atomicExch(&p.jump_slots[s_jump_slot], 0u);
+#ifdef VRC_TIME_STATS
+    if constexpr (kWgTiles == 1) __syncthreads();         // (several waves: the barrier inside publish_counters)
+    if (tid_end == 0) {
+        const int cls = s_life[2] ? 12 : 9;
+        atomicAdd(&g_time_stats[cls], s_life[0]);
+        atomicAdd(&g_time_stats[cls + 1], s_life[1] * (unsigned long long)kWgTiles);
+        atomicAdd(&g_time_stats[cls + 2], 1ULL);
+    }
+#endif
 }
 
 __global__ void reduce_counters_kernel(const unsigned long long *partials, int nblocks, unsigned long long *out) {
@@ -1016,12 +1058,32 @@ static bool svo_uses_coarse(const RaycastParams &p) {
     return p.coarse != nullptr && p.coarse_log2 >= 1 && p.coarse_log2 <= p.log2_dim - 2;
 }
 static bool svo_uses_boxes(const RaycastParams &p) { return svo_uses_coarse(p) && p.boxes != nullptr && p.box_aux != nullptr; }
-static size_t svo_stack_bytes(const RaycastParams &p) {
+// (every size below is per WORKGROUP of the instance that runs: `tiles` tiles of 64 threads -- svo_tiles_per_workgroup())
+static bool svo_jumps(const RaycastParams &p) { return p.jump_min_run < kJumpOff; }
+static int svo_tiles(bool jump, bool multi) { return svo_tiles_per_workgroup(jump, multi); }
+static size_t svo_stack_bytes(const RaycastParams &p, int tiles) {
     const int levels = svo_uses_coarse(p) ? p.log2_dim - p.coarse_log2 : (p.log2_dim > 1 ? p.log2_dim - 1 : 1);
     // (with the boxes: a dword per level and thread for the descriptor index, behind the 8-byte entries)
-    return (size_t)levels * kBlockThreads * (sizeof(uint64_t) + (svo_uses_boxes(p) ? sizeof(uint32_t) : 0)) + (size_t)p.lds_pad_bytes;
+    // (lds_pad_bytes is stated per 4-tile block: a workgroup takes its share, so the knob lowers the occupancy as it did)
+    return (size_t)levels * 64 * tiles * (sizeof(uint64_t) + (svo_uses_boxes(p) ? sizeof(uint32_t) : 0)) + (size_t)p.lds_pad_bytes * tiles / kTilesPerBlock;
 }
-constexpr size_t lds_table_bytes(int rows) { return (size_t)(3 * rows) * kBlockThreads * sizeof(JumpWord); }   // ring rows x 3 pairs, one 8-byte word per thread
+constexpr size_t lds_table_bytes(int rows, int tiles) { return (size_t)(3 * rows) * 64 * tiles * sizeof(JumpWord); }   // ring rows x 3 pairs, one 8-byte word per thread
+
+// workgroups the launch of this frame takes (one row of counter partials each) and the tiles of one: vrc_api.cpp sizes the
+// partials and the global table buffer's slots from these, after it has resolved jump_min_run and light_count
+// the scheduling knobs are at their defaults: the instances that have them compiled in (kTuned) render the frame
+static bool svo_tuned(const RaycastParams &p) {
+    const bool jump = svo_jumps(p), lds_tab = jump && p.jump_tables_lds > 0;
+    return (!jump || p.jump_min_run == (lds_tab ? kDefaultJumpMinRunLds : kDefaultJumpMinRun)) &&
+           p.widen_nodes != 0 && p.arith_mask != 0 && p.safe_run != 0 && p.single_step != 0 &&
+           p.shade_threshold == kDefaultShadeThreshold && p.safe_steps == (jump ? kDefaultSafeStepsJump : kDefaultSafeSteps) &&
+           p.exact_steps == kDefaultExactSteps && p.burst_steps == kDefaultBurstSteps;
+}
+// (the instances with run-time knobs exist with the multi-light code compiled in only)
+int raycast_workgroup_tiles(const RaycastParams &p) {
+    return (p.svo && p.stepping_mode == 0) ? svo_tiles(svo_jumps(p), p.light_count > 1 || !svo_tuned(p)) : kTilesPerBlock;
+}
+int raycast_workgroups(const RaycastParams &p) { return svo_workgroups(p.blocks_x * p.local_tile_rows, raycast_workgroup_tiles(p)); }
 
 // How many rows of the jumps' Euclid tables live in LDS for this frame: 3 when the jump instance with stack + tables still reaches
 // the blocks per CU its registers allow (VRC_MIN_BLOCKS_JUMP) -- asked of the runtime once per LDS size -- else 2 (the box instances
@@ -1038,7 +1100,8 @@ int jump_tables_lds_rows(const RaycastParams &p) {
     const bool box = svo_uses_boxes(p), multi = p.light_count > 1;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const size_t stack = svo_stack_bytes(p);
+    const int tiles = svo_tiles(true, multi);
+    const size_t stack = svo_stack_bytes(p, tiles);
     const unsigned long long key = ((unsigned long long)stack << 16) | ((unsigned long long)(dev & 0xff) << 8) | (box ? 2u : 0u) | (multi ? 4u : 0u);
     static unsigned long long cached_key[8] = {~0ULL, ~0ULL, ~0ULL, ~0ULL, ~0ULL, ~0ULL, ~0ULL, ~0ULL};
     static int cached[8];
@@ -1046,9 +1109,9 @@ int jump_tables_lds_rows(const RaycastParams &p) {
     if (cached_key[slot] != key) {
         auto fits = [&](const void *fn, int rows) {
             int per_cu = 0;
-            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlockThreads, stack + lds_table_bytes(rows));
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * tiles, stack + lds_table_bytes(rows, tiles));
             (void)hipGetLastError();
-            return e == hipSuccess && per_cu >= (multi ? VRC_MIN_BLOCKS_JUMP_MULTI : VRC_MIN_BLOCKS_JUMP);
+            return e == hipSuccess && per_cu >= svo_min_workgroups(true, multi);
         };
         const void *f3 = box ? (multi ? reinterpret_cast<const void *>(raycast_svo_kernel<true, true, true, 3, true, true>)
                                       : reinterpret_cast<const void *>(raycast_svo_kernel<true, false, true, 3, true, true>))
@@ -1082,11 +1145,9 @@ hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchReco
         const int lds_rows = jump ? p.jump_tables_lds : 0;       // (vrc_api.cpp has resolved the setting to 0 / 2 / 3 rows with jump_tables_lds_rows)
         if (lds_rows != 0 && lds_rows != 3 && !(lds_rows == 2 && svo_uses_boxes(p))) return hipErrorInvalidValue;
         const bool lds_tab = lds_rows > 0;
-        const size_t lds = svo_stack_bytes(p) + lds_table_bytes(lds_rows);
-        const bool tuned = (!jump || p.jump_min_run == (lds_tab ? kDefaultJumpMinRunLds : kDefaultJumpMinRun)) &&
-                           p.widen_nodes != 0 && p.arith_mask != 0 && p.safe_run != 0 && p.single_step != 0 &&
-                           p.shade_threshold == kDefaultShadeThreshold && p.safe_steps == (jump ? kDefaultSafeStepsJump : kDefaultSafeSteps) &&
-                           p.exact_steps == kDefaultExactSteps && p.burst_steps == kDefaultBurstSteps;
+        const bool tuned = svo_tuned(p);
+        const int tiles = raycast_workgroup_tiles(p), nwg = svo_workgroups(nblocks, tiles);
+        const size_t lds = svo_stack_bytes(p, tiles) + lds_table_bytes(lds_rows, tiles);
         if (jump && !lds_tab && (!p.jump_cache || !p.jump_slots || p.jump_slot_count < 1)) return hipErrorInvalidValue;
         // 24 instances: the knobs at their defaults (kTuned) x {no jumps | Euclid tables in global memory | in LDS} x {no table | coarse
         // table | + empty boxes} x {one light | multi-light}, jumps only with the table, the box instances also with a two-row ring in
@@ -1095,7 +1156,7 @@ hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchReco
         // tests and tools that move the knobs, and a frame rendered through them is the same frame
         // (the record is filled from the same argument list the launch is instantiated with)
 #define VRC_LAUNCH(...) do { record_svo_instance<__VA_ARGS__>(rec); \
-                             hipLaunchKernelGGL((raycast_svo_kernel<__VA_ARGS__>), dim3(nblocks), dim3(kBlockThreads), lds, stream, p); } while (0)
+                             hipLaunchKernelGGL((raycast_svo_kernel<__VA_ARGS__>), dim3(nwg), dim3(64 * tiles), lds, stream, p); } while (0)
 #define VRC_LAUNCH_MT(J, L, ...) do { if (!tuned) VRC_LAUNCH(J, true, false, L, __VA_ARGS__); else if (multi) VRC_LAUNCH(J, true, true, L, __VA_ARGS__); \
                                     else VRC_LAUNCH(J, false, true, L, __VA_ARGS__); } while (0)
         if (jump && !svo_uses_coarse(p)) return hipErrorInvalidValue;     // (vrc_api.cpp switches the jumps off where there is no table)
@@ -1124,7 +1185,8 @@ hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchReco
 hipError_t launch_reduce_counters(const unsigned long long *partials, int nblocks, unsigned long long *out,
                                   hipStream_t stream) {
     (void)hipGetLastError();                 // an error an earlier call left behind is not this launch's
-    hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(256), 0, stream, partials, nblocks, out);
+    // (one block: 64 rows per trip of its loop -- the exact SVO kernel leaves a row per single-tile workgroup, 32 640 for a 1080p frame)
+    hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(1024), 0, stream, partials, nblocks, out);
     return hipGetLastError();
 }
 

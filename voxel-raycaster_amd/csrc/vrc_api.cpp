@@ -115,7 +115,7 @@ struct vrc_caster {
     vrc::LaunchRecord last_launch = {};   // the kernel instance the last enqueued frame was launched with (vrc_last_kernel)
     bool last_frame_wrote_hits = false;   // d_hits belongs to the last enqueued frame (setting hit_records was on)
     float *d_viewport = nullptr; float *d_image = nullptr; int32_t *d_hits = nullptr; uint8_t *d_rgba8 = nullptr;
-    uint32_t *d_jump_cache = nullptr, *d_jump_slots = nullptr; int jump_slot_count = 0;   // Euclid tables of the exact closed-form jumps (exact_jump.hpp), per resident block
+    uint32_t *d_jump_cache = nullptr, *d_jump_slots = nullptr; int jump_slot_count = 0, jump_slot_threads = 0;   // Euclid tables of the exact closed-form jumps (exact_jump.hpp), per resident block
     int32_t width = 0, height = 0;
     bool sliced = false;                  // viewport / image / hits hold only this rank's rows
     int32_t buffer_rows = 0;              // rows the three buffers hold
@@ -373,25 +373,27 @@ int install_viewport(vrc_caster *h, int32_t width, int32_t height, const float *
 }
 
 // the per-ray Euclid tables of the exact closed-form jumps (exact_jump.hpp): kJumpTableDwordsPerLane dwords per lane of a
-// block SLOT.  Only resident blocks hold a slot (the kernel takes and returns them), so the buffer is sized for the chip,
-// not for the frame: at most kJumpSlots slots of 12 KB.
-int ensure_jump_cache(vrc_caster *h, int nblocks) {
-    // an eighth of the slots per XCD, each eighth at least as large as the number of blocks one XCD can hold at a time: its
-    // CUs x the 256-thread blocks a CU holds at most (MI355X: 32 x 8 = kJumpSlotsPerXcd; a larger part gets larger eighths, and
-    // the kernel's slot search is bounded in any case)
+// workgroup SLOT of wg_tiles tiles.  Only resident workgroups hold a slot (the kernel takes and returns them), so the buffer is sized
+// for the chip, not for the frame: 8 x 256 slots of 12 KB with 4-tile workgroups, 8 x 1024 of 3 KB with single-tile ones.
+int ensure_jump_cache(vrc_caster *h, int nblocks, int wg_tiles) {
+    // an eighth of the slots per XCD, each eighth at least as large as the number of workgroups one XCD can hold at a time: its
+    // CUs x the workgroups of this size a CU holds at most (MI355X: 32 x 8 = kJumpSlotsPerXcd 256-thread blocks, 32 x 32 waves; a
+    // larger part gets larger eighths, and the kernel's slot search is bounded in any case)
     int cus = 0, threads_per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) cus = 256;
     if (hipDeviceGetAttribute(&threads_per_cu, hipDeviceAttributeMaxThreadsPerMultiProcessor, h->device) != hipSuccess) threads_per_cu = 2048;
     (void)hipGetLastError();
-    const int per_xcd = std::max(vrc::kJumpSlotsPerXcd, ((cus + 7) / 8) * std::max(1, threads_per_cu / vrc::kBlockThreads));
+    const int wg_threads = 64 * wg_tiles;
+    const int per_xcd = std::max(vrc::kJumpSlotsPerXcd, ((cus + 7) / 8) * std::max(1, threads_per_cu / wg_threads));
     const int slots = 8 * std::max(1, std::min(nblocks, per_xcd));
-    if (h->d_jump_cache && h->jump_slot_count >= slots) return VRC_OK;
+    if (h->d_jump_cache && h->jump_slot_count >= slots && h->jump_slot_threads >= wg_threads) return VRC_OK;
     release(h->d_jump_cache); release(h->d_jump_slots);
     h->jump_slot_count = 0;
-    HIP_TRY(h, hipMalloc((void **)&h->d_jump_cache, (size_t)slots * vrc::kBlockThreads * vrc::kJumpTableDwordsPerLane * sizeof(uint32_t)));
+    HIP_TRY(h, hipMalloc((void **)&h->d_jump_cache, (size_t)slots * wg_threads * vrc::kJumpTableDwordsPerLane * sizeof(uint32_t)));
     HIP_TRY(h, hipMalloc((void **)&h->d_jump_slots, (size_t)slots * sizeof(uint32_t)));
     HIP_TRY(h, hipMemsetAsync(h->d_jump_slots, 0, (size_t)slots * sizeof(uint32_t), h->stream));
     h->jump_slot_count = slots;
+    h->jump_slot_threads = wg_threads;
     return VRC_OK;
 }
 
@@ -1291,14 +1293,6 @@ int compute_async_one(vrc_caster *h) {
     }
     p.local_tile_rows = local_rows;
     p.blocks_x = (h->width + vrc::kTileW * vrc::kTilesPerBlock - 1) / (vrc::kTileW * vrc::kTilesPerBlock);
-    const int nblocks = p.blocks_x * p.local_tile_rows;
-    if (nblocks > h->partial_blocks) {
-        release(h->d_partials);
-        h->partial_blocks = 0;
-        HIP_TRY(h, hipMalloc((void **)&h->d_partials, sizeof(unsigned long long) * vrc::kCtrCount * (size_t)nblocks));
-        h->partial_blocks = nblocks;
-    }
-    p.counters = h->d_partials;
     // What the kernels derive from the tree (the dense table of its top, the empty boxes) lives WITH the tree and is built by
     // vrc_prepare / vrc_validate; a frame that finds it missing or built for other settings builds it here (under the guard).
     if (svo) derive_from_tree(h, t, p.log2_dim, p.root_index, p.stepping_mode, p);
@@ -1314,8 +1308,18 @@ int compute_async_one(vrc_caster *h) {
                                                                             : vrc::kJumpOff)));
     p.safe_steps = (int32_t)std::min<int64_t>(256, std::max<int64_t>(2, setting_or(h, "safe_steps",
                                     p.jump_min_run < vrc::kJumpOff ? vrc::kDefaultSafeStepsJump : vrc::kDefaultSafeSteps)));
+    // one row of counter partials per WORKGROUP of the kernel that will run (the exact SVO kernel's are finer than a 4-tile block:
+    // vrc_params.h svo_tiles_per_workgroup), known now that the instance is: the partials, the reduction and the table slots follow it
+    const int nblocks = vrc::raycast_workgroups(p), wg_tiles = vrc::raycast_workgroup_tiles(p);
+    if (nblocks > h->partial_blocks) {
+        release(h->d_partials);
+        h->partial_blocks = 0;
+        HIP_TRY(h, hipMalloc((void **)&h->d_partials, sizeof(unsigned long long) * vrc::kCtrCount * (size_t)nblocks));
+        h->partial_blocks = nblocks;
+    }
+    p.counters = h->d_partials;
     if (svo && p.stepping_mode == 0 && p.jump_min_run < vrc::kJumpOff && !tables_in_lds) {
-        VRC_TRY(ensure_jump_cache(h, nblocks));
+        VRC_TRY(ensure_jump_cache(h, nblocks, wg_tiles));
         p.jump_cache = h->d_jump_cache; p.jump_slots = h->d_jump_slots; p.jump_slot_count = h->jump_slot_count;
     }
     h->last_frame_boxes = p.boxes != nullptr;

@@ -24,6 +24,8 @@ hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
 hipError_t launch_pack_rgba8(const float *image, uint8_t *out, size_t n_pixels, hipStream_t stream);
 hipError_t launch_frame_setup(const RaycastParams &p, hipStream_t stream);
 int jump_tables_lds_rows(const RaycastParams &p);
+int raycast_workgroup_tiles(const RaycastParams &p);
+int raycast_workgroups(const RaycastParams &p);
 hipError_t launch_raycast(const RaycastParams &p, hipStream_t stream, LaunchRecord *rec);
 hipError_t launch_reduce_counters(const unsigned long long *partials, int nblocks, unsigned long long *out,
                                   hipStream_t stream);

@@ -19,6 +19,21 @@ static_assert((kTileW & (kTileW - 1)) == 0 && kTileW >= 1 && kTileW <= 64, "tile
 #endif
 constexpr int kTilesPerBlock = VRC_TILES_PER_BLOCK;   // 256-thread block = 4 horizontally adjacent tiles (32x8 px)
 constexpr int kBlockThreads = 64 * kTilesPerBlock;
+// the exact SVO kernel's workgroup is finer than a block: a workgroup's wave slots, registers and LDS are only given back when its
+// LAST wave ends, and the lives of a block's four tiles differ (profiles/r07_block_imbalance.txt), so with one tile per workgroup a
+// finished tile makes room for the next at once.  The 4-tile block stays the unit of the tile map (block_pixel in
+// raycast_common.hpp: which XCD renders a tile, and in which order, is what it was), of blocks_x and of the occupancy knobs.
+// A function of the instance class so that a class that measures otherwise can keep coarser workgroups.
+#ifndef VRC_SVO_TILES
+#define VRC_SVO_TILES 1
+#endif
+constexpr int svo_tiles_per_workgroup(bool /*jump*/, bool /*multi*/) { return VRC_SVO_TILES; }
+static_assert(VRC_SVO_TILES >= 1 && VRC_TILES_PER_BLOCK % VRC_SVO_TILES == 0, "a workgroup is a whole fraction of a block");
+// workgroups a launch of `groups` blocks takes with `tiles` tiles per workgroup: the group count rounded up to a multiple of 8
+// where a group is split (the map keeps group g on XCD g % 8; the workgroups of the groups that do not exist render nothing)
+constexpr int svo_workgroups(int groups, int tiles) {
+    return tiles == kTilesPerBlock ? groups : ((groups + 7) / 8) * 8 * (kTilesPerBlock / tiles);
+}
 // defaults of the scheduling knobs (settings of the same names; the tuned kernel instances have them compiled in)
 // iterations per safe run (setting safe_steps): short rounds since round 4 -- with the tree's top in the coarse table a node
 // event is cheap, and what a long safe run costs is the lanes that idle through it (38 % lane utilisation at 64).  Headline
@@ -52,7 +67,7 @@ constexpr int kDefaultJumpMinDepthBoxes = 11;
 constexpr int kDefaultJumpMinRunLds = VRC_DEFAULT_JUMP_MIN_RUN_LDS;
 constexpr int kJumpOff = 1 << 24;      // jump_min_run >= this: the instances without the jump block
 constexpr int kJumpTableDwordsPerLane = 24;   // 4 ring rows x 3 pairs x one 8-byte word (exact_jump.hpp JumpWord; checked in raycast_kernel.hip)
-constexpr int kJumpSlotsPerXcd = 256;         // table slots per XCD: 32 CUs x 8 blocks, the most 256-thread blocks an XCD can hold at any occupancy
+constexpr int kJumpSlotsPerXcd = 256;         // table slots per XCD, at least: 32 CUs x 8 blocks, the most 256-thread blocks an XCD can hold at any occupancy
 constexpr int kJumpSlots = 8 * kJumpSlotsPerXcd;   // a block takes a slot of ITS XCD while it runs (the L2s of two XCDs are not coherent)
 constexpr int kMaxLights = 8;         // light slots (include/LightController.h:95)
 constexpr int kMaxLevels = 24;        // descriptor levels the LDS stack can hold (dim <= 2^24)
