@@ -459,6 +459,41 @@ int vrc_box_intersection_device(vrc_caster *h, const void *d_boxes, int64_t n, i
 int vrc_sweep_boxes(vrc_caster *h, const float *sweeps, int64_t n, int32_t max_events, uint32_t flags, int32_t *records);
 int vrc_sweep_boxes_device(vrc_caster *h, const void *d_sweeps, int64_t n, int32_t max_events, uint32_t flags, void *d_records);
 
+/* ---- voxel reads ---------------------------------------------------------- */
+
+/* What is in the scene?  Map::getVoxel (src/map/Map.cpp:25-29, a read of the reference's own host array) as a batch, and dense
+ * blocks of materials -- for a mesher, a physics engine's chunk cache, a minimap, a save file -- against the scene the handle
+ * renders, device-built trees included: those exist only on the GPU, so there is no host grid to look at.
+ *
+ * The material of voxel (x, y, z) is vrc_box_intersection's, and the branch follows using_octree: the array branch reads the
+ * byte at the frame's index x + dx * (y + dz * z) (an index past the array reads as 0, a position outside map_dim reads as 0);
+ * the SVO branch finds the voxel solid when it lies in a valid slot whose leaf bit is set, at any level, or in any valid slot
+ * at the bottom level, with the attachment byte (int8, sign kept) as the material for bottom-level descriptors when
+ * attachments are assigned, else 5; outside [0, dim)^3 is 0.  There is no STOPPING_ONLY filter: the caller gets the byte.
+ *
+ * vrc_get_voxels     positions int32[3 n], out int32[n]: out[i] = the material of voxel positions[3 i .. 3 i + 2], sign-extended.
+ * vrc_read_regions   n regions of one common size (sx, sy, sz), each axis >= 1; lo int32[3 n], region i covers
+ *                    [lo_i, lo_i + size) and owns bytes [i V, (i + 1) V) of out, V = sx sy sz:
+ *                      out[i V + (x - lo.x) + sx * ((y - lo.y) + sy * (z - lo.z))] = the material of (x, y, z)
+ *                    -- an int8[z][y][x] block, the layout vrc_build_dense_grid takes, so a scene can be read, changed on the
+ *                    host and built again.  Every one of the n V bytes is written, zeros included; a region may lie partly or
+ *                    wholly outside the map (that part is zeros: the one-voxel apron a mesher needs at the map's edge), and lo
+ *                    may be any int32.  n_bytes is the size of out and must be at least n V.
+ *
+ * Host rules as vrc_box_intersection: synchronous on the handle's stream (a frame in flight finishes first); the image, hit
+ * records, counters, timing and vrc_last_kernel are untouched; the coarse table is used when it is built and never built here,
+ * with the same results without it; rank 0's GPU for a group, the caller's device restored; the host calls' staging grows on
+ * demand and is freed by vrc_release_map / _octree / _viewport and vrc_destroy.  A read is one kernel launch with no scratch
+ * and no host wait before the end.  The _device variants take memory the handle's GPU can read and write and wait for the
+ * null stream first; positions, lo and the point output must be 4-byte aligned, the region output may have any alignment.
+ * Errors, with nothing launched: VRC_ERR_INVALID_ARGUMENT for a null handle or pointer, n < 0, a size component < 1, a
+ * misaligned 4-byte pointer or n_bytes < n V; VRC_ERR_LIMIT when n V overflows size_t (or exceeds 2^63);
+ * VRC_ERR_NOT_READY as for ray queries.  n = 0 succeeds.                                                                  */
+int vrc_get_voxels(vrc_caster *h, const int32_t *positions, int64_t n, int32_t *out);
+int vrc_get_voxels_device(vrc_caster *h, const void *d_positions, int64_t n, void *d_out);
+int vrc_read_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], int8_t *out, size_t n_bytes);
+int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], void *d_out, size_t n_bytes);
+
 /* Device pointers of the resident frame buffers (float4[w*h], int32[8*w*h]);
  * lets a host that owns the GPU (e.g. a torch process) consume the frame
  * without a PCIe round trip.                                                 */

@@ -181,6 +181,10 @@ SIGNATURES = {
     "vrc_box_intersection_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrc_sweep_boxes": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p]),
     "vrc_sweep_boxes_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
+    "vrc_get_voxels": (C.c_int, [_H, _i32p, C.c_int64, _i32p]),
+    "vrc_get_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vrc_read_regions": (C.c_int, [_H, _i32p, C.c_int64, _i32p, C.POINTER(C.c_int8), C.c_size_t]),
+    "vrc_read_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
@@ -813,6 +817,43 @@ class CLCaster:
         """sweep_boxes on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 9 float32 in, n x 8 int32 out)."""
         return self._ok(lib.vrc_sweep_boxes_device(self._h, C.c_void_p(sweeps_ptr), int(n), int(max_events),
                                                    SWEEP_STOPPING_ONLY if stopping_only else 0, C.c_void_p(records_ptr)))
+
+    # -- voxel reads (vrc_get_voxels / vrc_read_regions, include/vrc.h)
+    def get_voxels(self, positions: np.ndarray) -> np.ndarray:
+        """The material of each voxel: positions (n, 3) int32 = x, y, z -> (n,) int32 (0: empty or outside the map)."""
+        p = np.ascontiguousarray(positions, dtype=np.int32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise VrcError(f"get_voxels: positions must have shape (n, 3), got {p.shape}")
+        out = np.empty(p.shape[0], dtype=np.int32)
+        if not self._ok(lib.vrc_get_voxels(self._h, _ptr(p, _i32p), p.shape[0], _ptr(out, _i32p))):
+            raise VrcError(self.last_error())
+        return out
+
+    def get_voxels_device(self, positions_ptr: int, n: int, out_ptr: int) -> bool:
+        """get_voxels on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 3 int32 in, n int32 out)."""
+        return self._ok(lib.vrc_get_voxels_device(self._h, C.c_void_p(positions_ptr), int(n), C.c_void_p(out_ptr)))
+
+    def read_regions(self, lo: np.ndarray, size) -> np.ndarray:
+        """Dense blocks of materials: lo (n, 3) int32 = the regions' lower corners x, y, z, size = (sx, sy, sz) common to all
+        -> (n, sz, sy, sx) int8, so out[i, z - lo_z, y - lo_y, x - lo_x] is the material of (x, y, z); outside the map is 0."""
+        c = np.ascontiguousarray(lo, dtype=np.int32)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise VrcError(f"read_regions: lo must have shape (n, 3), got {c.shape}")
+        sz = np.ascontiguousarray(size, dtype=np.int32)
+        if sz.shape != (3,) or (sz < 1).any():
+            raise VrcError(f"read_regions: size must be three integers >= 1, got {size}")
+        out = np.empty((c.shape[0], int(sz[2]), int(sz[1]), int(sz[0])), dtype=np.int8)
+        if not self._ok(lib.vrc_read_regions(self._h, _ptr(c, _i32p), c.shape[0], _ptr(sz, _i32p), _ptr(out, C.POINTER(C.c_int8)), out.nbytes)):
+            raise VrcError(self.last_error())
+        return out
+
+    def read_regions_device(self, lo_ptr: int, n: int, size, out_ptr: int, n_bytes: int) -> bool:
+        """read_regions on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 3 int32 in, n_bytes >=
+        n * sx * sy * sz int8 out, any alignment)."""
+        sz = np.ascontiguousarray(size, dtype=np.int32)
+        if sz.shape != (3,):
+            raise VrcError(f"read_regions_device: size must be three integers, got {size}")
+        return self._ok(lib.vrc_read_regions_device(self._h, C.c_void_p(lo_ptr), int(n), _ptr(sz, _i32p), C.c_void_p(out_ptr), int(n_bytes)))
 
     def counters(self) -> dict:
         c = Counters()

@@ -152,6 +152,24 @@ public:
         return ok(vrc_sweep_boxes(h_, sweeps.data(), n, max_events, stopping_only ? VRC_SWEEP_STOPPING_ONLY : 0u, records.data()));
     }
 
+    // extension: Map::getVoxel (Map.cpp:25-29) as a batch against the resident scene (vrc_get_voxels): positions = 3 int32 each,
+    // materials = one int32 each
+    bool get_voxels(const std::vector<int32_t> &positions, std::vector<int32_t> &materials) {
+        const int64_t n = (int64_t)(positions.size() / 3);
+        materials.resize((size_t)n);
+        return ok(vrc_get_voxels(h_, positions.data(), n, materials.data()));
+    }
+    bool get_voxels_device(const void *d_positions, int64_t n, void *d_materials) { return ok(vrc_get_voxels_device(h_, d_positions, n, d_materials)); }
+    // ... and dense int8[z][y][x] blocks of one common size (vrc_read_regions): lo = 3 int32 per region, outside the map is 0
+    bool read_regions(const std::vector<int32_t> &lo, const int32_t size[3], std::vector<int8_t> &materials) {
+        const int64_t n = (int64_t)(lo.size() / 3);
+        materials.resize((size_t)n * (size_t)size[0] * (size_t)size[1] * (size_t)size[2]);
+        return ok(vrc_read_regions(h_, lo.data(), n, size, materials.data(), materials.size()));
+    }
+    bool read_regions_device(const void *d_lo, int64_t n, const int32_t size[3], void *d_materials, size_t n_bytes) {
+        return ok(vrc_read_regions_device(h_, d_lo, n, size, d_materials, n_bytes));
+    }
+
     int last_status() const { return status_; }
     std::string last_error() const { return h_ ? vrc_last_error(h_) : "not initialised"; }
     vrc_caster *handle() { return h_; }

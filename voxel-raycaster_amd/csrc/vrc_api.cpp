@@ -27,6 +27,7 @@
 #include "box_query.h"
 #include "box_sweep.h"
 #include "raycast_query.h"
+#include "voxel_read.h"
 #include "vrc_launch.h"
 #include "vrc_params.h"
 
@@ -136,6 +137,9 @@ struct vrc_caster {
     float *d_sweep_in = nullptr; int32_t *d_sweep_out = nullptr; int64_t sweep_io_capacity = 0;
     int32_t *d_sweep_rec = nullptr, *d_sweep_vox = nullptr; int64_t *d_sweep_cnt = nullptr, *d_sweep_scan = nullptr; int64_t sweep_capacity = 0;
     int64_t sweep_n_big = 0;
+    // vrc_get_voxels / vrc_read_regions: staging of the host calls (positions or corners in, values or bytes out)
+    int32_t *d_read_in = nullptr; int64_t read_in_capacity = 0;
+    void *d_read_out = nullptr; size_t read_out_bytes = 0;
 
     // live (retained) host pointers
     const float *cam_dir = nullptr, *cam_pos = nullptr;
@@ -199,10 +203,11 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
         }                                                                                         \
     } while (0)
 
-// vrc_cast_rays', vrc_box_intersection's and vrc_sweep_boxes' staging and scratch buffers (the caller's device is left as it was)
+// vrc_cast_rays', vrc_box_intersection's, vrc_sweep_boxes' and the voxel reads' staging and scratch buffers (the caller's device is left
+// as it was)
 void release_query_staging(vrc_caster *h) {
     if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp &&
-        !h->d_sweep_in && !h->d_sweep_rec) return;
+        !h->d_sweep_in && !h->d_sweep_rec && !h->d_read_in && !h->d_read_out) return;
     {
         DeviceRestore restore;
         (void)hipSetDevice(h->device);
@@ -213,6 +218,8 @@ void release_query_staging(vrc_caster *h) {
         h->box_io_capacity = 0; h->box_vox_bytes = 0; h->box_capacity = 0; h->box_item_capacity = 0; h->box_temp_bytes = 0;
         release(h->d_sweep_in); release(h->d_sweep_out); release(h->d_sweep_rec); release(h->d_sweep_vox); release(h->d_sweep_cnt); release(h->d_sweep_scan);
         h->sweep_io_capacity = 0; h->sweep_capacity = 0;
+        release(h->d_read_in); release(h->d_read_out);
+        h->read_in_capacity = 0; h->read_out_bytes = 0;
     }
     (void)hipGetLastError();
 }
@@ -2011,6 +2018,115 @@ int vrc_sweep_boxes_device(vrc_caster *h, const void *d_sweeps, int64_t n, int32
     VRC_TRY(sweep_enqueue(h, static_cast<const float *>(d_sweeps), n, max_events, flags, static_cast<int32_t *>(d_records)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return VRC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// voxel reads (vrc_get_voxels / vrc_read_regions and their _device variants, voxel_read.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the argument checks of the region reads, then the readiness checks of the ray queries; *total = n V, the bytes the call writes
+int region_check(vrc_caster *h, const void *lo, int64_t n, const int32_t size[3], const void *out, size_t n_bytes, size_t *total, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    if (!size) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null size", what);
+    for (int a = 0; a < 3; a++)
+        if (size[a] < 1) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: size[%d] = %d < 1", what, a, (int)size[a]);
+    if (n > 0 && (!lo || !out)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null corners or output", what);
+    size_t bytes = (size_t)size[0];
+    for (uint64_t f : {(uint64_t)size[1], (uint64_t)size[2], (uint64_t)n}) {
+        if (f != 0 && bytes > SIZE_MAX / f) return fail(h, VRC_ERR_LIMIT, "%s: n * size[0] * size[1] * size[2] bytes overflows size_t", what);
+        bytes *= (size_t)f;
+    }
+    if (bytes > (size_t)INT64_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^63 bytes", what);      // (the kernel counts its waves in int64)
+    if (n_bytes < bytes) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: output holds %zu bytes, the regions need %zu", what, n_bytes, bytes);
+    *total = bytes;
+    return query_check(h, lo, n, 0, 0, out, what);
+}
+
+// One launch on the handle's stream (current device: h->device).  The tree's guard is held until the kernel is enqueued, as
+// box_enqueue holds it; the coarse table is used when it is built for this tree, never built here.
+int read_enqueue(vrc_caster *h, const int32_t *d_in, int64_t n, const int32_t size[3], void *d_out) {
+    std::unique_lock<std::mutex> lock(h->tree->guard);
+    vrc::ReadParams q;
+    memset(&q, 0, sizeof(q));
+    q.positions = d_in; q.n = n;
+    bind_scene(h, h->tree.get(), q);
+    if (!size) {
+        q.values = static_cast<int32_t *>(d_out);
+        HIP_TRY(h, vrc::launch_voxel_points(q, h->stream));
+        return VRC_OK;
+    }
+    q.bytes = static_cast<int8_t *>(d_out);
+    for (int a = 0; a < 3; a++) {
+        q.size[a] = size[a];
+        q.bricks[a] = ((int64_t)size[a] + 6) / 8 + 1;     // the bricks a region touches per axis at most, whatever its alignment
+    }
+    // (n V fits size_t and a brick count is at most size + 1, so the wave count fits 64 bits with room to spare)
+    HIP_TRY(h, vrc::launch_voxel_regions(q, h->stream));
+    return VRC_OK;
+}
+
+// the host calls: stage in, one launch, stage out, wait
+int read_staged(vrc_caster *h, const int32_t *in, int64_t n, const int32_t size[3], void *out, size_t out_bytes) {
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    VRC_TRY(grow(h, h->read_in_capacity, n, {{h->d_read_in, sizeof(int32_t) * 3 * (size_t)n}}));
+    VRC_TRY(grow(h, h->read_out_bytes, out_bytes, {{h->d_read_out, out_bytes}}));
+    HIP_TRY(h, hipMemcpyAsync(h->d_read_in, in, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    VRC_TRY(read_enqueue(h, h->d_read_in, n, size, h->d_read_out));
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_read_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+// the _device calls: the pointers checked, the null stream's work first, one launch, wait
+int read_device(vrc_caster *h, const void *d_in, int64_t n, const int32_t size[3], void *d_out, const char *what) {
+    if (((uintptr_t)d_in & 3u) || (!size && ((uintptr_t)d_out & 3u)))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", what, size ? "the corners" : "positions and output");
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!query_pointer_ok(h, d_in) || !query_pointer_ok(h, d_out))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: input and output must be memory the GPU of the handle (device %d) can read and write", what, h->device);
+    VRC_TRY(wait_for_null_stream(h));
+    VRC_TRY(read_enqueue(h, static_cast<const int32_t *>(d_in), n, size, d_out));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_get_voxels(vrc_caster *h, const int32_t *positions, int64_t n, int32_t *out) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = query_check(h, positions, n, 0, 0, out, "get_voxels");
+    if (rc != VRC_OK || n == 0) return rc;
+    return read_staged(h, positions, n, nullptr, out, sizeof(int32_t) * (size_t)n);
+}
+
+int vrc_get_voxels_device(vrc_caster *h, const void *d_positions, int64_t n, void *d_out) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int rc = query_check(h, d_positions, n, 0, 0, d_out, "get_voxels_device");
+    if (rc != VRC_OK || n == 0) return rc;
+    return read_device(h, d_positions, n, nullptr, d_out, "get_voxels_device");
+}
+
+int vrc_read_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], int8_t *out, size_t n_bytes) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    size_t total = 0;
+    int rc = region_check(h, lo, n, size, out, n_bytes, &total, "read_regions");
+    if (rc != VRC_OK || n == 0) return rc;
+    return read_staged(h, lo, n, size, out, total);
+}
+
+int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], void *d_out, size_t n_bytes) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    size_t total = 0;
+    int rc = region_check(h, d_lo, n, size, d_out, n_bytes, &total, "read_regions_device");
+    if (rc != VRC_OK || n == 0) return rc;
+    return read_device(h, d_lo, n, size, d_out, "read_regions_device");
 }
 
 }  // extern "C"

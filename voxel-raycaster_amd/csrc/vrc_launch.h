@@ -1,6 +1,6 @@
 // Everything the host layer (vrc_api.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
 // vrc_api.cpp and by every file that defines one of these functions, so the compiler holds each definition against its
-// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h and box_query.h.
+// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h and voxel_read.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@ struct LaunchRecord;
 struct QueryParams;
 struct BoxParams;
 struct SweepParams;
+struct ReadParams;
 
 // raycast_kernel.hip
 hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
@@ -61,6 +62,10 @@ hipError_t box_scan(void *temp, size_t *temp_bytes, const int64_t *in, int64_t *
 // box_sweep.hip
 hipError_t launch_sweep_plan(const SweepParams &p, int64_t *big_cnt, hipStream_t stream);
 hipError_t launch_sweep(const SweepParams &p, hipStream_t stream);
+
+// voxel_read.hip
+hipError_t launch_voxel_points(const ReadParams &q, hipStream_t stream);
+hipError_t launch_voxel_regions(const ReadParams &q, hipStream_t stream);
 
 // svo_builder_gpu.hip
 int build_shell_terrain_device(hipStream_t stream, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
