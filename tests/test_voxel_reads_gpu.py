@@ -15,6 +15,7 @@ import pytest
 
 import box_replay as br
 import leaftree
+from relayout import with_materials as _with_materials
 import scenes
 import voxel_raycaster_amd as vrc
 import voxel_replay as vr
@@ -72,16 +73,6 @@ def _check_scene(c, mat, dim, regions, pts, tag):
     bad = np.nonzero(p != want)[0]
     assert bad.size == 0, (tag, pts[bad[:4]], p[bad[:4]], want[bad[:4]])
     return whole, apron, got, p
-
-
-def _with_materials(grid, seed):
-    """The scene's grid with a tenth of its solid voxels rewritten to 6 and a few to -3 (the sign must survive)."""
-    g = np.asarray(grid, np.int8).copy()
-    rng = np.random.default_rng(seed)
-    solid = np.nonzero(g)[0]
-    g[rng.choice(solid, size=max(1, solid.size // 10), replace=False)] = 6
-    g[rng.choice(solid, size=max(1, solid.size // 50), replace=False)] = -3
-    return g
 
 
 @pytest.mark.parametrize("make", scenes.ALL, ids=lambda m: m.__name__)
