@@ -1,10 +1,12 @@
 // Kernel-argument block of the batched box-overlap queries (vrc_box_intersection / vrc_box_intersection_device,
-// include/vrc.h), shared by the host layer (vrc_api.cpp) and box_query.hip.  The scene fields are those of QueryParams
-// (raycast_query.h) that a box query reads; the scratch pointers are the host layer's, sized from what the plan pass
-// reports.  Nothing of a frame's buffers is in here.
+// include/vrc.h), shared by the host layer (vrc_api.cpp) and box_query.hip.  The scene is a SceneView (vrc_params.h), as in
+// QueryParams (raycast_query.h); the scratch pointers are the host layer's, sized from what the plan pass reports.  Nothing
+// of a frame's buffers is in here.
 #pragma once
 
 #include <stdint.h>
+
+#include "vrc_params.h"
 
 namespace vrc {
 
@@ -34,18 +36,7 @@ struct BoxParams {
     int32_t *records;                 // int32[8 * n]
     int64_t *counts;                  // int64[n]
     int32_t *voxels;                  // int32[4 * max_voxels * n] (nullptr iff max_voxels == 0)
-    // scene (the branch and the tree as in QueryParams)
-    int32_t svo;
-    const int8_t *map;                // array branch
-    int32_t map_dim[3];
-    uint64_t map_bytes;
-    const uint64_t *descriptors;
-    uint64_t root_index;
-    int32_t log2_dim;
-    const uint32_t *attach_lookup;
-    const uint64_t *attachments;
-    const uint64_t *coarse;           // nullptr: descend from the root
-    int32_t coarse_log2;
+    SceneView scene;
     int32_t space_log2;               // the aligned space the items tile: 2^log2_dim (tree), the map's largest side rounded up (array)
     // scratch (device)
     BoxPlan *plan;                    // [n]

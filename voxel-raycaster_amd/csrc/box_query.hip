@@ -108,7 +108,7 @@ __global__ __launch_bounds__(kBoxThreads) void box_query_plan_kernel(const BoxPa
                 const int lo = (int)floorf(o[a]);
                 int hi = (int)ceilf(e[a]);
                 if (hi < lo + 1) hi = lo + 1;
-                const int dim = q.svo ? (1 << q.log2_dim) : q.map_dim[a];
+                const int dim = q.scene.svo ? (1 << q.scene.log2_dim) : q.scene.map_dim[a];
                 if (lo < 0 || hi > dim) pl.flags |= kBoxClipped;
                 pl.lo[a] = lo > 0 ? lo : 0;
                 pl.hi[a] = hi < dim ? hi : dim;

@@ -53,7 +53,7 @@ __device__ __forceinline__ bool sweep_is_wave(const SweepParams &p, const Sweep 
         int hi = (int)ceilf(w.e[a]);
         if (hi < lo + 1) hi = lo + 1;
         const int64_t x = (int64_t)hi - lo + 1;               // (the range of a moving axis breathes by one layer)
-        ext[a] = x < p.box.map_dim[a] ? x : p.box.map_dim[a];
+        ext[a] = x < p.box.scene.map_dim[a] ? x : p.box.scene.map_dim[a];
     }
     bool wave = false;
 #pragma unroll
@@ -123,7 +123,7 @@ __device__ __forceinline__ void sweep_run(const SweepParams &p, const Sweep &w, 
         bool clipped = false;
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-            dim[a] = p.box.map_dim[a];
+            dim[a] = p.box.scene.map_dim[a];
             lo[a] = (int)floorf(w.o[a]);
             hi[a] = (int)ceilf(w.e[a]);
             if (hi[a] < lo[a] + 1) hi[a] = lo[a] + 1;

@@ -2,7 +2,7 @@
 // queries (box_query.hip) and the swept-box queries (box_sweep.hip).  Device code only; each translation unit that includes
 // it gets its own copy (anonymous namespace).
 //
-// The walk (SVO branch) descends from the coarse table's cell (or the root) to the walk's node, then visits the node's subtree
+// The walk (SVO branch) descends from the coarse table's cell (or the root) to the walk's node (svo_node.hpp), then visits the node's subtree
 // in Morton order with a restart at every finished node -- stackless, so no LDS and no scratch.  Empty slots and slots outside
 // the range are skipped; a solid leaf (a valid leaf slot at any level, or any valid slot at the bottom level: query_locate's
 // rule, raycast_query.hip) is counted by volume; a solid cube that the range cuts is entered as a virtual node only to emit, so
@@ -13,18 +13,11 @@
 #include <hip/hip_runtime.h>
 
 #include "box_query.h"
-#include "vrc_params.h"
+#include "svo_node.hpp"
 
 namespace vrc {
 
 namespace {
-
-// the packed cursor entry of raycast_query.hip's query_entry: bits 0-7 valid mask, 8-15 leaf mask, 16-63 index of the first kept child
-__device__ __forceinline__ uint64_t box_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);
-}
 
 // length of [c, c + s) inside [lo, hi)
 __device__ __forceinline__ int overlap(int c, int s, int lo, int hi) {
@@ -46,34 +39,6 @@ __device__ __forceinline__ bool counted(const BoxParams &q, int mat) {
     return (q.flags & kBoxStoppingOnly) ? (mat == 5 || mat == 6) : mat != 0;
 }
 
-// the node of size 2^r at (cx, cy, cz) (r >= 1): 0 empty, 1 inside a solid leaf, 2 a descriptor (cur, its index)
-__device__ int region_descend(const BoxParams &q, int cx, int cy, int cz, int r, uint64_t &cur, uint64_t &cur_index) {
-    const int n = q.log2_dim;
-    int top;
-    cur_index = q.root_index;
-    if (q.coarse && r <= n - q.coarse_log2) {
-        const int csh = n - q.coarse_log2;
-        const uint64_t e = q.coarse[coarse_index((unsigned)(cx >> csh), (unsigned)(cy >> csh), (unsigned)(cz >> csh), q.coarse_log2)];
-        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
-        top = (int)(e >> kCoarseLevelShift);
-    } else {
-        cur = box_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
-        top = 0;
-    }
-    for (int guard = 0; guard <= n && n - top > r; guard++) {
-        const int b = n - top - 1;                        // (>= r >= 1: the child is never a single voxel)
-        const int i = ((cx >> b) & 1) | (((cy >> b) & 1) << 1) | (((cz >> b) & 1) << 2);
-        const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
-        if (!(masks & bit)) return 0;
-        if ((masks >> 8) & bit) return 1;
-        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
-        cur_index = (cur >> 16) + (uint64_t)rank;
-        cur = box_entry(q.descriptors, cur_index, q.descriptors[cur_index]);
-        top++;
-    }
-    return 2;
-}
-
 // kEmit = false: nothing is emitted
 struct NoSink {
     __device__ __forceinline__ void operator()(int64_t, int, int, int, int) const {}
@@ -85,7 +50,9 @@ template <bool kEmit, class Sink>
 __device__ void walk(const BoxParams &q, int cx, int cy, int cz, int r, const Range &rg, Acc &acc, int64_t base, int64_t limit,
                      Sink &sink) {
     uint64_t cur0 = 0, idx0 = 0;
-    const int state0 = q.svo ? region_descend(q, cx, cy, cz, r, cur0, idx0) : 2;
+    const SceneView &sc = q.scene;
+    // (r >= 1: never the single voxel of state 3)
+    const int state0 = sc.svo ? descend_to_node(sc, cx, cy, cz, r, cur0, idx0) : 2;
     if (state0 == 0) return;
     const uint64_t end = 1ULL << (3 * r);
     uint64_t p = 0;
@@ -102,13 +69,13 @@ __device__ void walk(const BoxParams &q, int cx, int cy, int cz, int r, const Ra
             if (wx && wy && wz) {
                 int kind = 0, mat = 5;                    // 0 empty, 1 solid, 2 a node to enter
                 uint64_t child = 0;
-                if (!q.svo) {
+                if (!sc.svo) {
                     if (cb > 0) {
                         kind = 2;
                     } else {
                         // the frame's index (y stride map_dim[2]); past the array reads as empty (raycast_query.hip)
-                        const uint64_t idx = (uint64_t)((long)x0 + (long)q.map_dim[0] * ((long)y0 + (long)q.map_dim[2] * z0));
-                        mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
+                        const uint64_t idx = (uint64_t)((long)x0 + (long)sc.map_dim[0] * ((long)y0 + (long)sc.map_dim[2] * z0));
+                        mat = idx < sc.map_bytes ? (int)sc.map[idx] : 0;
                         kind = 1;
                     }
                 } else if (solid) {
@@ -118,21 +85,19 @@ __device__ void walk(const BoxParams &q, int cx, int cy, int cz, int r, const Ra
                     if (masks & bit) {
                         if (((masks >> 8) & bit) || cb == 0) {
                             kind = 1;
-                            if (q.attach_lookup && cb == 0) {        // only bottom-level descriptors carry materials
-                                const uint64_t a = q.attachments[q.attach_lookup[cur_index]];
-                                mat = (int)(int8_t)(a >> (8 * i));
-                            }
+                            // only bottom-level descriptors carry materials (5 where none are assigned)
+                            if (cb == 0) mat = (int)(int8_t)(bottom_materials(sc, cur_index) >> (8 * i));
                         } else {
                             kind = 2;
-                            child = (cur >> 16) + (uint64_t)((unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u);
+                            child = kept_child(cur, (unsigned)i);
                         }
                     }
                 }
                 const bool whole = wx == s && wy == s && wz == s;
                 if (kind == 1 && kEmit && !whole) kind = 3;    // a solid cube the box cuts: entered virtually, to emit in order
                 if (kind >= 2) {
-                    if (kind == 2 && q.svo) {
-                        cur = box_entry(q.descriptors, child, q.descriptors[child]);
+                    if (kind == 2 && sc.svo) {
+                        cur = node_entry(sc.descriptors, child, sc.descriptors[child]);
                         cur_index = child;
                     }
                     solid = solid || kind == 3;

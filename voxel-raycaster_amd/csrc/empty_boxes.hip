@@ -29,8 +29,8 @@
 
 #include <chrono>
 
+#include "svo_node.hpp"
 #include "vrc_launch.h"
-#include "vrc_params.h"
 
 namespace vrc {
 
@@ -39,12 +39,6 @@ namespace {
 constexpr uint64_t kPosNone = ~0ULL;
 constexpr int kPosBits = 19;              // coordinates below 2^19; bits 57-61 hold the level
 constexpr int kPosLevelShift = 57;
-
-__device__ __forceinline__ uint64_t bx_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);        // bits 0-7 valid, 8-15 leaf, 16.. first child
-}
 
 __device__ __forceinline__ uint64_t pack_pos(int x, int y, int z, int level) {
     return (uint64_t)(unsigned)x | ((uint64_t)(unsigned)y << kPosBits) | ((uint64_t)(unsigned)z << (2 * kPosBits)) | ((uint64_t)level << kPosLevelShift);
@@ -63,7 +57,7 @@ __global__ void box_positions_kernel(const uint64_t *__restrict__ descriptors, u
     if (ps == kPosNone || (int)(ps >> kPosLevelShift) != level) return;
     const int half = 1 << (n - level - 1);
     if (half == 1) return;                                // the children are voxels
-    const uint64_t e = bx_entry(descriptors, idx, descriptors[idx]);
+    const uint64_t e = node_entry(descriptors, idx, descriptors[idx]);
     const unsigned valid = (unsigned)e & 0xffu, leaf = ((unsigned)e >> 8) & 0xffu;
     const int x = (int)(ps & ((1u << kPosBits) - 1u)), y = (int)((ps >> kPosBits) & ((1u << kPosBits) - 1u)), z = (int)((ps >> (2 * kPosBits)) & ((1u << kPosBits) - 1u));
     unsigned rank = 0;
@@ -77,8 +71,6 @@ __global__ void box_positions_kernel(const uint64_t *__restrict__ descriptors, u
         rank++;
     }
 }
-
-__device__ __forceinline__ int box_decode(unsigned c) { return c < 4u ? (int)c : (int)((4u | (c & 3u)) << ((c >> 2) - 1u)); }
 
 // children of the node at (ox, oy, oz) with child size `half` that meet the region [lo, hi)
 __device__ __forceinline__ unsigned overlap_mask(int ox, int oy, int oz, int half, const int lo[3], const int hi[3]) {
@@ -140,8 +132,8 @@ __device__ bool region_is_empty(const uint64_t *__restrict__ descriptors, const 
         const int half = 1 << (n - level - 1);
         if ((((unsigned)e >> 8) & (1u << k)) || half == 1) return false;      // a solid leaf / voxel that meets the region
         if (--budget < 0) { atomicAdd(&g_box_queries_cut, 1ULL); return false; }
-        const uint64_t child = (e >> 16) + (uint64_t)(__popc((unsigned)e & 0xffu & ((2u << k) - 1u)) - 1);
-        const uint64_t ce = bx_entry(descriptors, child, descriptors[child]);
+        const uint64_t child = kept_child(e, (unsigned)k);
+        const uint64_t ce = node_entry(descriptors, child, descriptors[child]);
         const int cx = ox + ((k & 1) ? half : 0), cy = oy + ((k & 2) ? half : 0), cz = oz + ((k & 4) ? half : 0);
         const unsigned ctodo = overlap_mask(cx, cy, cz, half >> 1, lo, hi) & (unsigned)ce & 0xffu;
         if (!ctodo) continue;                             // nothing of the child meets the region: no need to go down
@@ -178,7 +170,7 @@ __device__ uint32_t grow_box(const uint64_t *__restrict__ descriptors, const uin
             if (next > 31u && code[side] < 31u) next = 31u;
             // the box already reaches the map's edge on this side, or the code is exhausted
             if (next > 31u || (positive ? hi[a] >= dim : lo[a] <= 0)) { alive &= ~(1u << side); continue; }
-            const long long ext = (long long)box_decode(next) << b;     // (448 node sizes of a 2^23-voxel node do not fit an int)
+            const long long ext = (long long)box_extent(next) << b;     // (448 node sizes of a 2^23-voxel node do not fit an int)
             int slo[3] = {lo[0], lo[1], lo[2]}, shi[3] = {hi[0], hi[1], hi[2]};
             int new_edge;
             if (positive) { const long long e = (long long)org_hi[a] + ext; new_edge = e > dim ? dim : (int)e; slo[a] = hi[a]; shi[a] = new_edge; }
@@ -188,7 +180,7 @@ __device__ uint32_t grow_box(const uint64_t *__restrict__ descriptors, const uin
                 // (extent << b, in an int) never exceeds twice the map
                 const long long need = positive ? (long long)dim - org_hi[a] : (long long)org_lo[a];
                 unsigned c = code[side] + 1u;
-                while (c < next && ((long long)box_decode(c) << b) < need) c++;
+                while (c < next && ((long long)box_extent(c) << b) < need) c++;
                 next = c;
             }
             if (region_is_empty(descriptors, path, level + 1, nx, ny, nz, n, slo, shi)) {
@@ -227,13 +219,13 @@ __global__ void box_grow_kernel(const uint64_t *__restrict__ descriptors, uint64
             const int nx = (int)(ps & ((1u << kPosBits) - 1u)), ny = (int)((ps >> kPosBits) & ((1u << kPosBits) - 1u)), nz = (int)((ps >> (2 * kPosBits)) & ((1u << kPosBits) - 1u));
             // the entries of the descriptor's ancestors and its own, root first (the canonical descent toward the node)
             uint64_t path[kMaxLevels];
-            path[0] = bx_entry(descriptors, root_index, descriptors[root_index]);
+            path[0] = node_entry(descriptors, root_index, descriptors[root_index]);
             for (int l = 0; l < level; l++) {
                 const int bb = n - l - 1;
-                const int i = ((nx >> bb) & 1) | (((ny >> bb) & 1) << 1) | (((nz >> bb) & 1) << 2);
+                const int i = child_slot(nx, ny, nz, bb);
                 const uint64_t e = path[l];
-                const uint64_t child = (e >> 16) + (uint64_t)(__popc((unsigned)e & 0xffu & ((2u << i) - 1u)) - 1);
-                path[l + 1] = bx_entry(descriptors, child, descriptors[child]);
+                const uint64_t child = kept_child(e, (unsigned)i);
+                path[l + 1] = node_entry(descriptors, child, descriptors[child]);
             }
             word = grow_box(descriptors, path, level, nx, ny, nz, k, n);
         }
@@ -251,20 +243,20 @@ __global__ void box_aux_kernel(const uint64_t *__restrict__ descriptors, uint64_
     const int sh = n - lc;
     const int x = (int)((cell & ((1u << lc) - 1u)) << sh), y = (int)(((cell >> lc) & ((1u << lc) - 1u)) << sh), z = (int)((cell >> (2 * lc)) << sh);
     uint64_t own = root_index, rec = box_child ? 0 : root_index;     // the descriptor, and its box record
-    uint64_t cur = bx_entry(descriptors, root_index, descriptors[root_index]);
+    uint64_t cur = node_entry(descriptors, root_index, descriptors[root_index]);
     int top = 0;
     uint32_t out = 0;
     for (;;) {
         if (top == lc) { out = top < box_levels ? (uint32_t)rec : 0u; break; }
         const int b = n - top - 1;
-        const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+        const int i = child_slot(x, y, z, b);
         const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
         if (!(masks & bit)) { out = top < box_levels ? boxes[rec * 8 + (uint64_t)i] : 0u; break; }   // empty above the table's level: its box
         if ((masks >> 8) & bit) { out = 0; break; }                             // solid leaf
-        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
+        const unsigned rank = child_rank(masks, (unsigned)i);
         own = (cur >> 16) + (uint64_t)rank;
         rec = box_child ? (top + 1 < box_levels ? (uint64_t)box_child[rec] + rank : 0) : own;
-        cur = bx_entry(descriptors, own, descriptors[own]);
+        cur = node_entry(descriptors, own, descriptors[own]);
         top++;
     }
     aux[coarse_index((unsigned)(cell & ((1u << lc) - 1u)), (unsigned)((cell >> lc) & ((1u << lc) - 1u)), (unsigned)(cell >> (2 * lc)), lc)] = out;
@@ -299,8 +291,8 @@ __global__ void box_check_kernel(const uint64_t *__restrict__ descriptors, uint6
     lo[2] = (int)((ps >> (2 * kPosBits)) & ((1u << kPosBits) - 1u)) + ((k & 4) ? s : 0);
     const uint32_t w = boxes[rec * 8 + (uint64_t)k];
     for (int a = 0; a < 3; a++) {
-        hi[a] = lo[a] + s + (box_decode((w >> (15 + 5 * a)) & 31u) << b);
-        lo[a] -= box_decode((w >> (5 * a)) & 31u) << b;
+        hi[a] = lo[a] + s + (box_extent((w >> (15 + 5 * a)) & 31u) << b);
+        lo[a] -= box_extent((w >> (5 * a)) & 31u) << b;
         if (lo[a] < 0) lo[a] = 0;
         if (hi[a] > dim) hi[a] = dim;
     }
@@ -309,15 +301,15 @@ __global__ void box_check_kernel(const uint64_t *__restrict__ descriptors, uint6
     int v[3];
     for (int a = 0; a < 3; a++) v[a] = lo[a] + (int)((r2 >> (20 * a)) % (uint64_t)(hi[a] - lo[a]));
     if (r1 & 8u) { const int a = (int)((r1 >> 4) % 3u); v[a] = (r1 & 64u) ? hi[a] - 1 : lo[a]; }
-    uint64_t cur = bx_entry(descriptors, root_index, descriptors[root_index]);
+    uint64_t cur = node_entry(descriptors, root_index, descriptors[root_index]);
     for (int top = 0;; top++) {
         const int bb = n - top - 1;
-        const int i = ((v[0] >> bb) & 1) | (((v[1] >> bb) & 1) << 1) | (((v[2] >> bb) & 1) << 2);
+        const int i = child_slot(v[0], v[1], v[2], bb);
         const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
         if (!(masks & bit)) return;                       // empty: as promised
         if (((masks >> 8) & bit) || bb == 0) { atomicAdd(&result[1], 1ULL); return; }
-        const uint64_t child = (cur >> 16) + (uint64_t)(__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1);
-        cur = bx_entry(descriptors, child, descriptors[child]);
+        const uint64_t child = kept_child(cur, (unsigned)i);
+        cur = node_entry(descriptors, child, descriptors[child]);
     }
 }
 
@@ -331,24 +323,24 @@ __global__ void box_check_cells_kernel(const uint64_t *__restrict__ descriptors,
     const int sh = n - lc, dim = 1 << n;
     const unsigned ccx = (unsigned)(cell & ((1u << lc) - 1u)), ccy = (unsigned)((cell >> lc) & ((1u << lc) - 1u)), ccz = (unsigned)(cell >> (2 * lc));
     const int x = (int)(ccx << sh), y = (int)(ccy << sh), z = (int)(ccz << sh);
-    uint64_t cur = bx_entry(descriptors, root_index, descriptors[root_index]);
+    uint64_t cur = node_entry(descriptors, root_index, descriptors[root_index]);
     int b = 0;
     for (int top = 0;; top++) {
         if (top == lc) return;                            // the descent goes on below the table: no word for this cell
         b = n - top - 1;
-        const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+        const int i = child_slot(x, y, z, b);
         const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
         if (!(masks & bit)) break;                        // the empty node of 2^b voxels around the cell
         if ((masks >> 8) & bit) return;
-        const uint64_t child = (cur >> 16) + (uint64_t)(__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1);
-        cur = bx_entry(descriptors, child, descriptors[child]);
+        const uint64_t child = kept_child(cur, (unsigned)i);
+        cur = node_entry(descriptors, child, descriptors[child]);
     }
     const uint32_t w = aux[coarse_index(ccx, ccy, ccz, lc)];
     const int nm = ~((1 << b) - 1);
     long long lo[3] = {x & nm, y & nm, z & nm}, hi[3];
     for (int a = 0; a < 3; a++) {
-        hi[a] = lo[a] + (1LL << b) + ((long long)box_decode((w >> (15 + 5 * a)) & 31u) << b);
-        lo[a] -= (long long)box_decode((w >> (5 * a)) & 31u) << b;
+        hi[a] = lo[a] + (1LL << b) + ((long long)box_extent((w >> (15 + 5 * a)) & 31u) << b);
+        lo[a] -= (long long)box_extent((w >> (5 * a)) & 31u) << b;
         if (lo[a] < 0) lo[a] = 0;
         if (hi[a] > dim) hi[a] = dim;
     }
@@ -356,15 +348,15 @@ __global__ void box_check_cells_kernel(const uint64_t *__restrict__ descriptors,
     int v[3];
     for (int a = 0; a < 3; a++) v[a] = (int)(lo[a] + (long long)((r2 >> (20 * a)) % (uint64_t)(hi[a] - lo[a])));
     if (r1 & 8u) { const int a = (int)((r1 >> 4) % 3u); v[a] = (int)((r1 & 64u) ? hi[a] - 1 : lo[a]); }
-    cur = bx_entry(descriptors, root_index, descriptors[root_index]);
+    cur = node_entry(descriptors, root_index, descriptors[root_index]);
     for (int top = 0;; top++) {
         const int bb = n - top - 1;
-        const int i = ((v[0] >> bb) & 1) | (((v[1] >> bb) & 1) << 1) | (((v[2] >> bb) & 1) << 2);
+        const int i = child_slot(v[0], v[1], v[2], bb);
         const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
         if (!(masks & bit)) return;
         if (((masks >> 8) & bit) || bb == 0) { atomicAdd(&result[1], 1ULL); return; }
-        const uint64_t child = (cur >> 16) + (uint64_t)(__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1);
-        cur = bx_entry(descriptors, child, descriptors[child]);
+        const uint64_t child = kept_child(cur, (unsigned)i);
+        cur = node_entry(descriptors, child, descriptors[child]);
     }
 }
 
@@ -398,7 +390,7 @@ __global__ void box_bfs_emit_kernel(const uint64_t *__restrict__ descriptors, in
     const uint64_t rec = first + t, idx = desc_of[rec];
     child[rec] = 0;
     if (idx == kPosNone) return;
-    const uint64_t e = bx_entry(descriptors, idx, descriptors[idx]);
+    const uint64_t e = node_entry(descriptors, idx, descriptors[idx]);
     const unsigned valid = (unsigned)e & 0xffu, leaf = ((unsigned)e >> 8) & 0xffu;
     const unsigned nv = (unsigned)__popc(valid);
     if (!nv) return;

@@ -16,16 +16,12 @@
 #include <hip/hip_runtime.h>
 
 #include "raycast_common.hpp"
+#include "svo_node.hpp"
 #include "vrc_launch.h"
 
 namespace vrc {
 
 namespace {
-__device__ __forceinline__ uint64_t jump_make_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);
-}
 enum JumpLane { jStep = 0, jShade = 1, jDone = 2, jRelight = 3, jDescend = 4, jTable = 5 };
 
 // (coarse_index(): vrc_params.h -- measured, headline frame, table levels 8 / 9 / 10: plain x-fastest order 0.639 / 0.581 / 0.555 ms,
@@ -41,18 +37,18 @@ __global__ void coarse_build_kernel(const uint64_t *__restrict__ descriptors, ui
     const unsigned ccx = (unsigned)(cell & ((1u << lc) - 1u)), ccy = (unsigned)((cell >> lc) & ((1u << lc) - 1u)), ccz = (unsigned)(cell >> (2 * lc));
     const int x = (int)(ccx << sh), y = (int)(ccy << sh), z = (int)(ccz << sh);
     const uint64_t idx = coarse_index(ccx, ccy, ccz, lc);
-    uint64_t cur = jump_make_entry(descriptors, root_index, descriptors[root_index]);
+    uint64_t cur = node_entry(descriptors, root_index, descriptors[root_index]);
     int top = 0;
     while (top < lc) {
         const int b = n - top - 1;
-        const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+        const int i = child_slot(x, y, z, b);
         const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
         if (!(masks & bit) || ((masks >> 8) & bit)) break;    // empty or leaf: the descent block's test finds it from here
-        const uint64_t child = (cur >> 16) + (uint64_t)(__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1);
-        cur = jump_make_entry(descriptors, child, descriptors[child]);
+        const uint64_t child = kept_child(cur, (unsigned)i);
+        cur = node_entry(descriptors, child, descriptors[child]);
         top++;
     }
-    out[idx] = cur | ((uint64_t)top << kCoarseLevelShift);
+    out[idx] = coarse_cell_pack(cur, top);
 }
 
 // blocks per CU the register budget is set for: 8 waves per SIMD (64 VGPRs, 14 dwords of scratch) measured fastest --
@@ -128,7 +124,7 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
     // the root's entry is the same for every ray of the frame: it lives in scalar registers
     uint64_t root_entry;
     {
-        const uint64_t e = jump_make_entry(descriptors, p.root_index, descriptors[p.root_index]);
+        const uint64_t e = node_entry(descriptors, p.root_index, descriptors[p.root_index]);
         root_entry = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(e >> 32)) << 32) |
                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)e);
     }
@@ -145,15 +141,15 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
         pvx = x; pvy = y; pvz = z;
         for (;;) {
             const int b = n - top - 1;
-            const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+            const int i = child_slot(x, y, z, b);
             const unsigned masks = (unsigned)cur & 0xffffu;
             const unsigned bit = 1u << i;
             if (!(masks & bit)) return b;
             if (((masks >> 8) & bit) || b == 0) return -1;
-            const uint64_t child = (cur >> 16) + (uint64_t)(__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1);
+            const uint64_t child = kept_child(cur, (unsigned)i);
             const uint64_t d = descriptors[child];
             c_desc++;
-            cur = jump_make_entry(descriptors, child, d);
+            cur = node_entry(descriptors, child, d);
             if (top < n - 2) lds_stack[top * kBlockThreads + tid] = cur;     // the deepest entry is never popped to
             top++;
         }
@@ -163,8 +159,8 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
         uint64_t node = p.root_index;
         if (top > 0) {
             const uint64_t parent = (top == 1) ? root_entry : lds_stack[(top - 2) * kBlockThreads + tid];
-            const int slot = ((x >> 1) & 1) | (((y >> 1) & 1) << 1) | (((z >> 1) & 1) << 2);
-            node = (parent >> 16) + (uint64_t)(__popc((unsigned)parent & 0xffu & ((2u << slot) - 1u)) - 1);
+            const int slot = child_slot(x, y, z, 1);
+            node = kept_child(parent, (unsigned)slot);
         }
         const uint64_t a = p.attachments[p.attach_lookup[node]];
         return (int)(int8_t)(a >> (8 * ((x & 1) | ((y & 1) << 1) | ((z & 1) << 2))));
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
         };
         auto descend_body = [&]() {
                 const int b = n - top - 1;
-                const int i = ((r.vx >> b) & 1) | (((r.vy >> b) & 1) << 1) | (((r.vz >> b) & 1) << 2);
+                const int i = child_slot(r.vx, r.vy, r.vz, b);
                 const unsigned masks = (unsigned)cur & 0xffffu;
                 const unsigned bit = 1u << i;
                 if (!(masks & bit)) {                             // the voxel lies in an empty node of size 2^b
@@ -291,10 +287,10 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
                         mode = (r.distance_traveled < r.max_distance) ? jStep : ended();
                     }
                 } else {                                          // one level down: one dependent load
-                    const uint64_t child = (cur >> 16) + (uint64_t)(__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1);
+                    const uint64_t child = kept_child(cur, (unsigned)i);
                     const uint64_t d = descriptors[child];
                     c_desc++;
-                    cur = jump_make_entry(descriptors, child, d);
+                    cur = node_entry(descriptors, child, d);
                     if (top < n - 2) lds_stack[top * kBlockThreads + tid] = cur;     // the deepest entry is never popped to
                     top++;
                 }
@@ -312,8 +308,8 @@ __global__ __launch_bounds__(kBlockThreads, VRC_JUMP_MIN_BLOCKS) void raycast_ju
         if (kCoarse && mode == jTable) {
                 const uint64_t e = p.coarse[coarse_index((unsigned)(r.vx >> csh), (unsigned)(r.vy >> csh), (unsigned)(r.vz >> csh), lc)];
                 c_desc++;
-                cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
-                top = (int)(e >> kCoarseLevelShift);
+                cur = coarse_cell_entry(e);
+                top = coarse_cell_level(e);
                 if (top == lc) lds_stack[(lc - 1) * kBlockThreads + tid] = cur;      // pops inside the cell end here (lc <= n - 2)
                 mode = jDescend;
                 descend_body();

@@ -39,6 +39,7 @@
 #include "exact_jump.hpp"
 #include "raycast_common.hpp"
 #include "safe_run.hpp"
+#include "svo_node.hpp"
 #include "vrc_launch.h"
 
 #ifndef VRC_RELIGHT_THRESHOLD
@@ -48,15 +49,6 @@
 namespace vrc {
 
 static_assert(3 * 4 * (int)(sizeof(JumpWord) / sizeof(uint32_t)) == kJumpTableDwordsPerLane, "vrc_api.cpp sizes the global Euclid tables (4 ring rows x 3 pairs x 8 bytes) with kJumpTableDwordsPerLane");
-
-// Packed stack entry of one descriptor level:
-//   bits 0-7 valid mask, 8-15 leaf mask, 16-63 absolute index of the first kept child
-__device__ __forceinline__ uint64_t make_entry(const uint64_t *__restrict__ descriptors, uint64_t index,
-                                               uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);        // (leaf<<8 | valid) are bits 16..31 of d
-}
 
 // ---------------------------------------------------------------------------
 // dense-array branch
@@ -285,7 +277,9 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
     uint32_t *const lds_own = reinterpret_cast<uint32_t *>(lds_stack + (size_t)(kCoarse ? n - lc : (n > 1 ? n - 1 : 1)) * kWgThreads);
     uint32_t boxw = 0;
     // the empty child i of a node with valid mask `valid`, widened over the empty siblings that lie ahead of the ray (enter_node's
-    // rule for the box-less instances), as a box word: extent code 1 -- one node size -- on the side the ray leaves through
+    // rule for the box-less instances), as a box word: extent code 1 -- one node size -- on the side the ray leaves through.
+    // (svo_node.hpp's widened_box_word(widen_axes()) written out, here and in enter_node: as calls the rule compiles to a different
+    // instruction stream in 12 of this file's instances -- profiles/r10_descriptor_header.txt)
     auto widen_word = [&](unsigned valid, int i) -> uint32_t {
         const unsigned sgn = ((unsigned)r.flags >> kFlagStepShift) & 7u, ahead = ((unsigned)i ^ sgn) & 7u;
         auto span = [&](unsigned e) -> unsigned { return ((unsigned)(0xFF5533110F050301ULL >> (8u * e)) & 0xffu) << ((unsigned)i & ~e); };
@@ -312,8 +306,8 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
             const uint64_t cell = coarse_index((unsigned)(x >> csh), (unsigned)(y >> csh), (unsigned)(z >> csh), lc);   // (vrc_params.h: 32-bit arithmetic in the default layout)
             const uint64_t e = p.coarse[cell];
             if (kBox) own = p.box_aux[cell];
-            cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
-            top = (int)(e >> kCoarseLevelShift);
+            cur = coarse_cell_entry(e);
+            top = coarse_cell_level(e);
             c_desc += (unsigned)(top - a);
             if (top == lc) {                              // slot 0 = level lc: pops inside the cell end here
                 lds_stack[tid] = cur;
@@ -329,7 +323,7 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
         pvx = x; pvy = y; pvz = z;
         for (;;) {
             const int b = n - top - 1;
-            const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+            const int i = child_slot(x, y, z, b);
             const unsigned masks = (unsigned)cur & 0xffffu;
             const unsigned bit = 1u << i;
             if (!(masks & bit)) {
@@ -342,14 +336,14 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
                 return b;
             }
             if (((masks >> 8) & bit) || b == 0) return -1;
-            const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
+            const unsigned rank = child_rank(masks, (unsigned)i);
             const uint64_t child = (cur >> 16) + (uint64_t)rank;
             const uint64_t d = descriptors[child];
             // the child's box record: the descriptor index itself, or (upper levels only) the parent's first-child record + the rank
             // -- a load beside the descriptor's, not behind it
             if (kBox) own = p.box_child ? (top + 1 < p.box_levels ? p.box_child[own] + rank : 0u) : (uint32_t)child;
             c_desc++;
-            cur = make_entry(descriptors, child, d);
+            cur = node_entry(descriptors, child, d);
             lds_stack[(top + 1 - sbase) * kWgThreads + tid] = cur;   // level top+1 (>= lc + 1 with the table)
             if (kBox) lds_own[(top + 1 - sbase) * kWgThreads + tid] = own;
             top++;
@@ -361,8 +355,8 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
         uint64_t node = p.root_index;
         if (top > 0) {
             const uint64_t parent = (!kCoarse && top == 1) ? root_entry : lds_stack[(top - 1 - sbase) * kWgThreads + tid];
-            const int slot = ((x >> 1) & 1) | (((y >> 1) & 1) << 1) | (((z >> 1) & 1) << 2);
-            node = (parent >> 16) + (uint64_t)(__popc((unsigned)parent & 0xffu & ((2u << slot) - 1u)) - 1);
+            const int slot = child_slot(x, y, z, 1);
+            node = kept_child(parent, (unsigned)slot);
         }
         const uint64_t a = p.attachments[p.attach_lookup[node]];
         return (int)(int8_t)(a >> (8 * ((x & 1) | ((y & 1) << 1) | ((z & 1) << 2))));
@@ -388,7 +382,7 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
             // to the map (beyond it everything is empty, but the :563 bounds test must see the crossing)
             auto side = [&](bool pos, int v, int axis, int dim, int &base, float &count) {
                 const unsigned c = (boxw >> (unsigned)(5 * axis + (pos ? 15 : 0))) & 31u;
-                const int ext = (c < 4u ? (int)c : (int)((4u | (c & 3u)) << ((c >> 2) - 1u))) << b;
+                const int ext = box_extent(c) << b;
                 const int o = v & ~(size - 1);
                 if (pos) { const int f = o + size + ext; base = f < dim ? f : dim; count = (float)(base - v); }
                 else { const int f = o - ext; base = (f > 0 ? f : 0) - 1; count = (float)(v - base); }
@@ -399,7 +393,7 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
             return;
         }
         const unsigned valid = (unsigned)cur & 0xffu;
-        const int i = ((pvx >> b) & 1) | (((pvy >> b) & 1) << 1) | (((pvz >> b) & 1) << 2);
+        const int i = child_slot(pvx, pvy, pvz, b);
         // axis a can be widened when the ray moves from this half of the parent toward the other half: child bit a differs
         // from the sign bit of the step (voxel_step is +1 or -1, never 0)
         const unsigned sgn = ((unsigned)r.flags >> kFlagStepShift) & 7u;
@@ -449,7 +443,7 @@ __global__ __launch_bounds__(64 * svo_tiles_per_workgroup(kJump, kMulti), svo_wa
             r.flags |= kFlagPrimary;
             const uint64_t d = descriptors[p.root_index];
             c_desc = 1;
-            root_entry = make_entry(descriptors, p.root_index, d);
+            root_entry = node_entry(descriptors, p.root_index, d);
             cur = root_entry;
             int b = -1;
             steps_to_flags();
@@ -955,6 +949,7 @@ __global__ void reduce_counters_kernel(const unsigned long long *partials, int n
 // get_oct_vox(camera voxel) (ray_caster_kernel.cl:140-251, 342-354): identical
 // for every pixel, so one lane evaluates it per frame and leaves the bias
 // (sub_oct_pos - voxel) * resolution / 2 plus its read count in p.frame.
+// (svo_node.hpp's get_oct_vox written out: as a call this kernel's instruction stream changes, and this file's is kept as it was)
 __global__ void frame_setup_kernel(const RaycastParams p) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int pos[3], corner[3] = {0, 0, 0};

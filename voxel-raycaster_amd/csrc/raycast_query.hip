@@ -17,6 +17,7 @@
 #include "raycast_common.hpp"
 #include "raycast_query.h"
 #include "safe_run.hpp"
+#include "svo_node.hpp"
 #include "vrc_launch.h"
 
 namespace vrc {
@@ -26,60 +27,38 @@ namespace {
 // iterations per safe run: the recovery bound of safe_run.hpp then allows thresholds up to 2^16
 constexpr int kQuerySafeSteps = 64;
 
-// the packed cursor entry of the SVO kernel: bits 0-7 valid mask, 8-15 leaf mask, 16-63 absolute index of the first kept child
-__device__ __forceinline__ uint64_t query_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);
-}
-
 // frame_setup_kernel's get_oct_vox(camera voxel) bias (ray_caster_kernel.cl:342-354) for a camera at `o`
 __device__ void origin_bias(const QueryParams &q, const float o[3], int bias[3]) {
-    int pos[3], corner[3] = {0, 0, 0};
+    int pos[3];
     for (int a = 0; a < 3; a++) pos[a] = (int)floorf(o[a]);
-    uint64_t index = q.root_index, d = q.descriptors[index];
-    int dimension = 1 << q.log2_dim, res = dimension / 2;
-    while (dimension > 1) {
-        const int half = dimension / 2;
-        int i = 0;
-        for (int a = 0; a < 3; a++)
-            if (pos[a] >= corner[a] + half) { i |= 1 << a; corner[a] += half; }
-        if (!((d >> (16 + i)) & 1ULL)) break;             // not valid: empty node
-        if ((d >> (24 + i)) & 1ULL) break;                // valid leaf: resolution not halved
-        dimension = half;
-        res /= 2;
-        const int before = __popcll((d >> 16) & ((2ULL << i) - 1ULL)) - 1;
-        const uint64_t base = (d & 0x8000ULL) ? q.descriptors[index + (d & 0x7fffULL)] : index + (d & 0x7fffULL);
-        index = base + (uint64_t)before;
-        d = q.descriptors[index];
-    }
-    for (int a = 0; a < 3; a++) bias[a] = q.octree_bias ? (corner[a] - pos[a]) * res / 2 : 0;
+    const OctVox v = get_oct_vox(q.scene.descriptors, q.scene.root_index, 1 << q.scene.log2_dim, pos);
+    for (int a = 0; a < 3; a++) bias[a] = q.octree_bias ? (v.corner[a] - pos[a]) * v.resolution / 2 : 0;
 }
 
 // The node of voxel (x, y, z), inside the map.  Returns b >= 0 when the voxel lies in an empty node of size 2^b, with the
 // per-axis countdowns to the face of its empty box (or of the node widened over empty siblings) on the sides the ray leaves
 // through (`pos` bit a: the ray moves toward +a); -1 when the voxel is solid, with its material (attachments: see vrc.h).
 __device__ int query_locate(const QueryParams &q, int x, int y, int z, unsigned pos, int cnt[3], int &mat) {
-    const int n = q.log2_dim;
-    const bool coarse = q.coarse != nullptr, box = q.boxes != nullptr;
-    const int lc = coarse ? q.coarse_log2 : 0;
-    uint64_t cur, cur_index = q.root_index;
+    const int n = q.scene.log2_dim;
+    const bool coarse = q.scene.coarse != nullptr, box = q.boxes != nullptr;
+    const int lc = coarse ? q.scene.coarse_log2 : 0;
+    uint64_t cur, cur_index = q.scene.root_index;
     int top;
     uint32_t own = 0;                                     // box: the cell's box word (top < lc) or the record of `cur`'s descriptor
     if (coarse) {
         const int csh = n - lc;
         const uint64_t cell = coarse_index((unsigned)(x >> csh), (unsigned)(y >> csh), (unsigned)(z >> csh), lc);
-        const uint64_t e = q.coarse[cell];
+        const uint64_t e = q.scene.coarse[cell];
         if (box) own = q.box_aux[cell];
-        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
-        top = (int)(e >> kCoarseLevelShift);
+        cur = coarse_cell_entry(e);
+        top = coarse_cell_level(e);
     } else {
-        cur = query_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
+        cur = node_entry(q.scene.descriptors, q.scene.root_index, q.scene.descriptors[q.scene.root_index]);
         top = 0;
     }
     for (int guard = 0; guard <= n; guard++) {            // (n + 1 levels at most: a corrupt tree cannot loop)
         const int b = n - top - 1;
-        const int i = ((x >> b) & 1) | (((y >> b) & 1) << 1) | (((z >> b) & 1) << 2);
+        const int i = child_slot(x, y, z, b);
         const unsigned masks = (unsigned)cur & 0xffffu;
         const unsigned bit = 1u << i;
         if (!(masks & bit)) {
@@ -91,15 +70,7 @@ __device__ int query_locate(const QueryParams &q, int x, int y, int z, unsigned 
             } else {
                 // the empty child widened over the empty siblings that lie ahead of the ray (the SVO kernel's rule), as a box word:
                 // extent code 1 -- one node size -- on the side the ray leaves through
-                const unsigned valid = masks & 0xffu, ahead = ((unsigned)i ^ pos) & 7u;
-                auto span = [&](unsigned e) -> unsigned { return ((unsigned)(0xFF5533110F050301ULL >> (8u * e)) & 0xffu) << ((unsigned)i & ~e); };
-                auto pair = [&](unsigned e) -> unsigned { return (1u << i) | (1u << ((unsigned)i ^ e)); };
-                unsigned ext = 0;
-                if ((span(ahead) & valid) == 0) ext = ahead;
-                else if ((ahead & 2u) && (pair(2u) & valid) == 0) ext = 2u;
-                else if ((ahead & 1u) && (pair(1u) & valid) == 0) ext = 1u;
-                else if ((ahead & 4u) && (pair(4u) & valid) == 0) ext = 4u;
-                for (unsigned a = 0; a < 3; a++) w |= ((ext >> a) & 1u) << (5u * a + (((pos >> a) & 1u) ? 15u : 0u));
+                w = widened_box_word(widen_axes(masks & 0xffu, (unsigned)i, ((unsigned)i ^ pos) & 7u), pos);
             }
             // the node at (v & ~(size - 1)) extended by the word's extents, clamped to the map (the bounds test must see the crossing)
             const int size = 1 << b, dim = 1 << n;
@@ -107,7 +78,7 @@ __device__ int query_locate(const QueryParams &q, int x, int y, int z, unsigned 
             for (int a = 0; a < 3; a++) {
                 const bool p = (pos >> a) & 1u;
                 const unsigned c = (w >> (unsigned)(5 * a + (p ? 15 : 0))) & 31u;
-                const int ext = (c < 4u ? (int)c : (int)((4u | (c & 3u)) << ((c >> 2) - 1u))) << b;
+                const int ext = box_extent(c) << b;
                 const int o = v[a] & ~(size - 1);
                 if (p) { const int f = o + size + ext; cnt[a] = (f < dim ? f : dim) - v[a]; }
                 else { const int f = o - ext; cnt[a] = v[a] - ((f > 0 ? f : 0) - 1); }
@@ -115,17 +86,14 @@ __device__ int query_locate(const QueryParams &q, int x, int y, int z, unsigned 
             return b;
         }
         if (((masks >> 8) & bit) || b == 0) {
-            mat = 5;
-            if (q.attach_lookup && top == n - 1) {            // only bottom-level descriptors carry materials
-                const uint64_t a = q.attachments[q.attach_lookup[cur_index]];
-                mat = (int)(int8_t)(a >> (8 * ((x & 1) | ((y & 1) << 1) | ((z & 1) << 2))));
-            }
+            // only bottom-level descriptors carry materials
+            mat = top == n - 1 ? (int)(int8_t)(bottom_materials(q.scene, cur_index) >> (8 * child_slot(x, y, z, 0))) : 5;
             return -1;
         }
-        const unsigned rank = (unsigned)__popc(masks & 0xffu & ((bit << 1) - 1u)) - 1u;
+        const unsigned rank = child_rank(masks, (unsigned)i);
         const uint64_t child = (cur >> 16) + (uint64_t)rank;
         if (box) own = q.box_child ? (top + 1 < q.box_levels ? q.box_child[own] + rank : 0u) : (uint32_t)child;
-        cur = query_entry(q.descriptors, child, q.descriptors[child]);
+        cur = node_entry(q.scene.descriptors, child, q.scene.descriptors[child]);
         cur_index = child;
         top++;
     }
@@ -177,15 +145,15 @@ __global__ __launch_bounds__(kQueryThreads) void raycast_query_kernel(const Quer
         // countdowns to the face of the known-empty region: a lookup is due when one runs out (1: after every step)
         int cnt[3] = {1, 1, 1};
         int mat = 0;
-        const bool inside0 = v[0] >= 0 && v[1] >= 0 && v[2] >= 0 && v[0] < q.map_dim[0] && v[1] < q.map_dim[1] && v[2] < q.map_dim[2];
-        if (q.svo && inside0 && query_locate(q, v[0], v[1], v[2], pos, cnt, mat) < 0) cnt[0] = cnt[1] = cnt[2] = 1;
+        const bool inside0 = v[0] >= 0 && v[1] >= 0 && v[2] >= 0 && v[0] < q.scene.map_dim[0] && v[1] < q.scene.map_dim[1] && v[2] < q.scene.map_dim[2];
+        if (q.scene.svo && inside0 && query_locate(q, v[0], v[1], v[2], pos, cnt, mat) < 0) cnt[0] = cnt[1] = cnt[2] = 1;
 
         int dist = 0, fm = 0, status = kRayStepCap;
         float m = 0.0f;
         while (dist < q.cap) {                                                     // :357
             // safe run: deep inside an empty box the iterations need no countdowns (safe_run.hpp); the gate stays closed for
             // delta_t < 1 (|d| > 1), for t beyond the recovery bound and for the +inf axes' thresholds
-            if (q.svo && q.cap - dist > kQuerySafeSteps && (cnt[0] | cnt[1] | cnt[2]) > 1) {
+            if (q.scene.svo && q.cap - dist > kQuerySafeSteps && (cnt[0] | cnt[1] | cnt[2]) > 1) {
                 float T = INFINITY;
                 for (int a = 0; a < 3; a++)
                     if (dt[a] != INFINITY) T = fminf(T, safe_threshold(t[a], dt[a], (float)cnt[a]));
@@ -222,19 +190,19 @@ __global__ __launch_bounds__(kQueryThreads) void raycast_query_kernel(const Quer
             cnt[0] -= fx; cnt[1] -= fy; cnt[2] -= fz;
             fm = fx | (fy << 1) | (fz << 2);
             if (cnt[0] == 0 || cnt[1] == 0 || cnt[2] == 0) {
-                if (v[0] >= q.map_dim[0] || v[1] >= q.map_dim[1] || v[2] >= q.map_dim[2] || v[0] < 0 || v[1] < 0 || v[2] < 0) {
+                if (v[0] >= q.scene.map_dim[0] || v[1] >= q.scene.map_dim[1] || v[2] >= q.scene.map_dim[2] || v[0] < 0 || v[1] < 0 || v[2] < 0) {
                     status = kRayLeftMap;                                          // :563-568
                     break;
                 }
-                if (q.svo) {
+                if (q.scene.svo) {
                     if (query_locate(q, v[0], v[1], v[2], pos, cnt, mat) < 0) {
                         if (mat == 5 || mat == 6) { status = kRayHit; break; }    // :575
                         cnt[0] = cnt[1] = cnt[2] = 1;                              // any other material is passed through
                     }
                 } else {
                     // :569 (the reference's index, y stride map_dim[2]; a non-cubic map can put it past the array: read as empty)
-                    const uint64_t idx = (uint64_t)((long)v[0] + (long)q.map_dim[0] * ((long)v[1] + (long)q.map_dim[2] * v[2]));
-                    mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
+                    const uint64_t idx = (uint64_t)((long)v[0] + (long)q.scene.map_dim[0] * ((long)v[1] + (long)q.scene.map_dim[2] * v[2]));
+                    mat = idx < q.scene.map_bytes ? (int)q.scene.map[idx] : 0;
                     if (mat == 5 || mat == 6) { status = kRayHit; break; }
                     cnt[0] = cnt[1] = cnt[2] = 1;                                  // the next step is tested again
                 }

@@ -24,14 +24,14 @@
 
 #include "../../include/vrc.h"
 #include "shell_scene.hpp"
+#include "svo_node.hpp"
 
 namespace {
 using vrc::lattice;
 using vrc::splitmix64;
-
-constexpr uint64_t kFarBit = 0x8000ULL;
-constexpr uint64_t kLeafAll = 0xFF000000ULL;
-constexpr uint64_t kValidAll = 0x00FF0000ULL;
+using vrc::kFarBit;
+using vrc::kLeafAll;
+using vrc::kValidAll;
 
 struct Node {
     uint64_t desc = 0;
@@ -302,16 +302,12 @@ void walk_materials(const uint64_t *desc, uint64_t index, int x, int y, int z, i
         attach.push_back(packed);
         return;
     }
-    const uint64_t base = (d & kFarBit) ? desc[index + (d & 0x7fff)] : index + (d & 0x7fff);
+    const uint64_t entry = vrc::node_entry(desc, index, d);
     const int h = size / 2;
-    int before = 0;
-    for (int k = 0; k < 8; k++) {
-        if (!(valid & (1u << k))) continue;
-        if (!(leaf & (1u << k)))
-            walk_materials(desc, base + (uint64_t)before, x + ((k & 1) ? h : 0), y + ((k & 2) ? h : 0), z + ((k & 4) ? h : 0), h,
+    for (int k = 0; k < 8; k++)
+        if ((valid & (1u << k)) && !(leaf & (1u << k)))
+            walk_materials(desc, vrc::kept_child(entry, (unsigned)k), x + ((k & 1) ? h : 0), y + ((k & 2) ? h : 0), z + ((k & 4) ? h : 0), h,
                            mat, lookup, attach);
-        before++;
-    }
 }
 
 template <class MaterialFn>
@@ -511,26 +507,10 @@ int vrc_scene_atlas(int32_t width, int32_t height, uint8_t *rgba8) {
 int vrc_octree_get_voxel(const uint64_t *descriptors, uint64_t root_index, uint32_t dim, const int32_t position[3],
                          int32_t *found, int32_t *resolution, int32_t sub_oct_pos[3]) {
     if (!descriptors || !position || !is_pow2(dim)) return VRC_ERR_INVALID_ARGUMENT;
-    uint64_t index = root_index, d = descriptors[index];
-    int32_t dimension = (int32_t)dim, res = dimension / 2, corner[3] = {0, 0, 0};
-    int hit = 1;
-    while (dimension > 1) {
-        const int32_t half = dimension / 2;
-        int i = 0;
-        for (int a = 0; a < 3; a++)
-            if (position[a] >= corner[a] + half) { i |= 1 << a; corner[a] += half; }
-        if (!((d >> 16) & (1ULL << i))) { hit = 0; break; }
-        if ((d >> 24) & (1ULL << i)) break;
-        dimension = half;
-        res /= 2;
-        const int before = __builtin_popcountll((d >> 16) & ((2ULL << i) - 1)) - 1;
-        const uint64_t base = (d & kFarBit) ? descriptors[index + (d & 0x7fff)] : index + (d & 0x7fff);
-        index = base + (uint64_t)before;
-        d = descriptors[index];
-    }
-    if (found) *found = hit;
-    if (resolution) *resolution = res;
-    if (sub_oct_pos) for (int a = 0; a < 3; a++) sub_oct_pos[a] = corner[a];
+    const vrc::OctVox v = vrc::get_oct_vox(descriptors, root_index, (int)dim, position);
+    if (found) *found = v.found;
+    if (resolution) *resolution = v.resolution;
+    if (sub_oct_pos) for (int a = 0; a < 3; a++) sub_oct_pos[a] = v.corner[a];
     return VRC_OK;
 }
 

@@ -33,6 +33,7 @@
 
 #include "../../include/vrc.h"
 #include "shell_scene.hpp"
+#include "svo_node.hpp"
 #include "vrc_launch.h"
 
 namespace vrc {
@@ -42,7 +43,6 @@ namespace {
 constexpr int kMaxDepth = 16;
 constexpr int kBrickLog2 = 6;             // largest brick: 64^3 voxels (the walk's frame arrays); the builders use 32^3 / 16^3
 constexpr int kMaxFrames = kBrickLog2;    // node sizes 2^kb .. 4
-constexpr uint64_t kFarBit = 0x8000ULL, kLeafAll = 0xFF000000ULL, kValidAll = 0x00FF0000ULL;
 
 struct Pyramid {
     const uint16_t *hi[kMaxDepth + 1];    // level l: max h over cells of 2^l x 2^l columns, (dim >> l)^2 entries
@@ -223,12 +223,10 @@ __global__ void scatter_kernel(const uint64_t *__restrict__ kv, uint64_t n, uint
 __device__ __forceinline__ int tree_holds(const uint64_t *desc, uint64_t root_index, int depth, uint32_t x, uint32_t y, uint32_t z) {
     uint64_t index = root_index, d = desc[index];
     for (int l = depth - 1;; l--) {                            // l = log2 of the child's size
-        const uint32_t i = ((x >> l) & 1u) | (((y >> l) & 1u) << 1) | (((z >> l) & 1u) << 2);
+        const uint32_t i = (uint32_t)child_slot((int)x, (int)y, (int)z, l);
         if (!((d >> (16 + i)) & 1ULL)) return 0;
         if (((d >> (24 + i)) & 1ULL) || l == 0) return 1;
-        const uint64_t at = index + (d & 0x7fffULL);
-        const uint64_t first = (d & kFarBit) ? desc[at] : at;
-        index = first + (uint64_t)(__popcll((d >> 16) & ((2ULL << i) - 1ULL)) - 1);
+        index = first_child(desc, index, d) + (uint64_t)child_rank((unsigned)(d >> 16), i);
         d = desc[index];
     }
 }
@@ -343,10 +341,8 @@ __global__ void attach_scan_kernel(uint32_t *chunk_count, uint64_t n_chunks, uns
 __device__ __forceinline__ uint64_t tree_block_descriptor(const uint64_t *desc, uint64_t root_index, int depth, uint32_t x, uint32_t y, uint32_t z) {
     uint64_t index = root_index, d = desc[index];
     for (int l = depth - 1; l >= 1; l--) {
-        const uint32_t i = ((x >> l) & 1u) | (((y >> l) & 1u) << 1) | (((z >> l) & 1u) << 2);
-        const uint64_t at = index + (d & 0x7fffULL);
-        const uint64_t first = (d & kFarBit) ? desc[at] : at;
-        index = first + (uint64_t)(__popcll((d >> 16) & ((2ULL << i) - 1ULL)) - 1);
+        const uint32_t i = (uint32_t)child_slot((int)x, (int)y, (int)z, l);
+        index = first_child(desc, index, d) + (uint64_t)child_rank((unsigned)(d >> 16), i);
         d = desc[index];
     }
     return index;

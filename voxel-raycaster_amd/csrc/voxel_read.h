@@ -1,9 +1,11 @@
 // Kernel-argument block of the voxel reads (vrc_get_voxels / vrc_read_regions and their _device variants, include/vrc.h),
-// shared by the host layer (vrc_api.cpp) and voxel_read.hip.  The scene fields are those of BoxParams (box_query.h) under the
-// same names, so the host layer binds them the same way.  There is no scratch: a read is one launch.
+// shared by the host layer (vrc_api.cpp) and voxel_read.hip.  The scene is a SceneView (vrc_params.h), as in BoxParams
+// (box_query.h).  There is no scratch: a read is one launch.
 #pragma once
 
 #include <stdint.h>
+
+#include "vrc_params.h"
 
 namespace vrc {
 
@@ -17,18 +19,7 @@ struct ReadParams {
     int8_t *bytes;                    // regions: int8[n * size[0] * size[1] * size[2]], any alignment
     int32_t size[3];                  // regions: the common size (sx, sy, sz), each >= 1
     int64_t bricks[3];                // regions: bricks a region can touch per axis, (size + 6) / 8 + 1
-    // scene (the branch and the tree as in BoxParams)
-    int32_t svo;
-    const int8_t *map;                // array branch
-    int32_t map_dim[3];
-    uint64_t map_bytes;
-    const uint64_t *descriptors;
-    uint64_t root_index;
-    int32_t log2_dim;
-    const uint32_t *attach_lookup;
-    const uint64_t *attachments;
-    const uint64_t *coarse;           // nullptr: descend from the root
-    int32_t coarse_log2;
+    SceneView scene;
 };
 
 }  // namespace vrc

@@ -5,7 +5,7 @@
 // byte for bottom-level descriptors when attachments are assigned, else 5.  Outside the map is 0.  One launch per call: no plan
 // pass, no scan, no scratch, no LDS.
 //
-//   voxel_points_kernel    one lane per point: region_descend's descent (from the coarse cell when the table is there) taken
+//   voxel_points_kernel    one lane per point: svo_node.hpp's descent (from the coarse cell when the table is there) taken
 //                          down to the voxel
 //   voxel_regions_kernel   one wave per (region, brick): a brick is a map-aligned 8^3 cube, one level-3 node.  A region touches
 //                          at most (size + 6) / 8 + 1 bricks per axis whatever its alignment, so the waves are numbered over
@@ -17,71 +17,24 @@
 //                          byte stores otherwise, never a read-modify-write (the neighbouring bytes are other waves').
 #include <hip/hip_runtime.h>
 
+#include "svo_node.hpp"
 #include "voxel_read.h"
 #include "vrc_launch.h"
-#include "vrc_params.h"
 
 namespace vrc {
 
 namespace {
 
-// the packed cursor entry of box_walk.hpp's box_entry: bits 0-7 valid mask, 8-15 leaf mask, 16-63 index of the first kept child
-__device__ __forceinline__ uint64_t read_entry(const uint64_t *__restrict__ descriptors, uint64_t index, uint64_t d) {
-    uint64_t base = index + (d & 0x7fffULL);
-    if (d & 0x8000ULL) base = descriptors[base];          // far pointer: the slot holds an absolute index
-    return (base << 16) | ((d >> 16) & 0xffffULL);
-}
-
-// index of the kept child in slot `bit` of the node `cur`
-__device__ __forceinline__ uint64_t kept_child(uint64_t cur, unsigned bit) {
-    const unsigned masks = (unsigned)cur & 0xffu;
-    return (cur >> 16) + (uint64_t)((unsigned)__popc(masks & ((bit << 1) - 1u)) - 1u);
-}
-
-// box_walk.hpp's region_descend for the node of size 2^r at (cx, cy, cz) inside the map, r >= 0: 0 empty, 1 inside a solid leaf,
-// 2 a descriptor (cur, its index; r >= 1), 3 a single solid voxel of a bottom-level descriptor (r == 0: cur is its parent)
-__device__ __forceinline__ int read_descend(const ReadParams &q, int cx, int cy, int cz, int r, uint64_t &cur, uint64_t &cur_index) {
-    const int n = q.log2_dim;
-    int top;
-    cur_index = q.root_index;
-    if (q.coarse && r <= n - q.coarse_log2) {
-        const int csh = n - q.coarse_log2;
-        const uint64_t e = q.coarse[coarse_index((unsigned)(cx >> csh), (unsigned)(cy >> csh), (unsigned)(cz >> csh), q.coarse_log2)];
-        cur = e & ((1ULL << kCoarseLevelShift) - 1ULL);
-        top = (int)(e >> kCoarseLevelShift);
-    } else {
-        cur = read_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
-        top = 0;
-    }
-    for (int guard = 0; guard <= n && n - top > r; guard++) {             // (n + 1 levels at most: a corrupt tree cannot loop)
-        const int b = n - top - 1;
-        const int i = ((cx >> b) & 1) | (((cy >> b) & 1) << 1) | (((cz >> b) & 1) << 2);
-        const unsigned masks = (unsigned)cur & 0xffffu, bit = 1u << i;
-        if (!(masks & bit)) return 0;
-        if (b == 0) return 3;
-        if ((masks >> 8) & bit) return 1;
-        cur_index = kept_child(cur, bit);
-        cur = read_entry(q.descriptors, cur_index, q.descriptors[cur_index]);
-        top++;
-    }
-    return 2;
-}
-
-// the 8 materials of the bottom-level descriptor at `index` (one byte per child slot; only the valid slots are looked at)
-__device__ __forceinline__ uint64_t bottom_materials(const ReadParams &q, uint64_t index) {
-    return q.attach_lookup ? q.attachments[q.attach_lookup[index]] : 0x0505050505050505ULL;
-}
-
 // The 2^kLevel voxels along x of row (y, z) of the node `cur` (at `index`, of size 2^kLevel), one byte each, lowest x first.
 template <int kLevel>
-__device__ __forceinline__ uint64_t resolve_row(const ReadParams &q, uint64_t cur, uint64_t index, int y, int z) {
+__device__ __forceinline__ uint64_t resolve_row(const SceneView &s, uint64_t cur, uint64_t index, int y, int z) {
     constexpr int cb = kLevel - 1;                        // the children are 2^cb voxels wide
     const int yz = (((y >> cb) & 1) << 1) | (((z >> cb) & 1) << 2);
     const unsigned masks = (unsigned)cur & 0xffffu;
     uint64_t row = 0;
     if constexpr (kLevel == 1) {
         if (masks & (3u << yz)) {
-            const uint64_t mats = bottom_materials(q, index);
+            const uint64_t mats = bottom_materials(s, index);
             for (int h = 0; h < 2; h++)
                 if (masks & (1u << (yz | h))) row |= ((mats >> (8 * (yz | h))) & 0xffULL) << (8 * h);
         }
@@ -94,8 +47,8 @@ __device__ __forceinline__ uint64_t resolve_row(const ReadParams &q, uint64_t cu
                 if ((masks >> 8) & bit) {
                     half = solid;
                 } else {
-                    const uint64_t child = kept_child(cur, bit);
-                    half = resolve_row<kLevel - 1>(q, read_entry(q.descriptors, child, q.descriptors[child]), child, y, z);
+                    const uint64_t child = kept_child(cur, (unsigned)(yz | h));
+                    half = resolve_row<kLevel - 1>(s, node_entry(s.descriptors, child, s.descriptors[child]), child, y, z);
                 }
             }
             row |= half << (8 * h * (1 << cb));
@@ -106,15 +59,15 @@ __device__ __forceinline__ uint64_t resolve_row(const ReadParams &q, uint64_t cu
 
 // array branch: voxels (x .. x + 7, y, z) by the frame's index (y stride map_dim[2]); past the array and outside map_dim reads as 0
 __device__ __forceinline__ uint64_t array_row(const ReadParams &q, int64_t x, int64_t y, int64_t z) {
-    if (y < 0 || y >= q.map_dim[1] || z < 0 || z >= q.map_dim[2]) return 0;
-    const int64_t base = x + (int64_t)q.map_dim[0] * (y + (int64_t)q.map_dim[2] * z);
-    if (x >= 0 && x + 8 <= q.map_dim[0] && (uint64_t)base + 8u <= q.map_bytes && (((uintptr_t)q.map + (uint64_t)base) & 7u) == 0)
-        return *reinterpret_cast<const uint64_t *>(q.map + base);
+    if (y < 0 || y >= q.scene.map_dim[1] || z < 0 || z >= q.scene.map_dim[2]) return 0;
+    const int64_t base = x + (int64_t)q.scene.map_dim[0] * (y + (int64_t)q.scene.map_dim[2] * z);
+    if (x >= 0 && x + 8 <= q.scene.map_dim[0] && (uint64_t)base + 8u <= q.scene.map_bytes && (((uintptr_t)q.scene.map + (uint64_t)base) & 7u) == 0)
+        return *reinterpret_cast<const uint64_t *>(q.scene.map + base);
     uint64_t row = 0;
     for (int k = 0; k < 8; k++) {
         const int64_t xx = x + k;
         const uint64_t idx = (uint64_t)(base + k);
-        if (xx >= 0 && xx < q.map_dim[0] && idx < q.map_bytes) row |= (uint64_t)(uint8_t)q.map[idx] << (8 * k);
+        if (xx >= 0 && xx < q.scene.map_dim[0] && idx < q.scene.map_bytes) row |= (uint64_t)(uint8_t)q.scene.map[idx] << (8 * k);
     }
     return row;
 }
@@ -131,20 +84,12 @@ __global__ __launch_bounds__(kReadThreads) void voxel_points_kernel(const ReadPa
     for (int64_t i = (int64_t)blockIdx.x * kReadThreads + threadIdx.x; i < q.n; i += stride) {
         const int x = q.positions[3 * i], y = q.positions[3 * i + 1], z = q.positions[3 * i + 2];
         int mat = 0;
-        if (q.svo) {
-            const int dim = 1 << q.log2_dim;
-            if (x >= 0 && y >= 0 && z >= 0 && x < dim && y < dim && z < dim) {
-                uint64_t cur = 0, index = 0;
-                const int state = read_descend(q, x, y, z, 0, cur, index);
-                if (state == 1) mat = 5;
-                if (state == 3) {
-                    const int slot = (x & 1) | ((y & 1) << 1) | ((z & 1) << 2);
-                    mat = (int)(int8_t)(bottom_materials(q, index) >> (8 * slot));
-                }
-            }
-        } else if (x >= 0 && y >= 0 && z >= 0 && x < q.map_dim[0] && y < q.map_dim[1] && z < q.map_dim[2]) {
-            const uint64_t idx = (uint64_t)((int64_t)x + (int64_t)q.map_dim[0] * ((int64_t)y + (int64_t)q.map_dim[2] * z));
-            mat = idx < q.map_bytes ? (int)q.map[idx] : 0;
+        if (q.scene.svo) {
+            const int dim = 1 << q.scene.log2_dim;
+            if (x >= 0 && y >= 0 && z >= 0 && x < dim && y < dim && z < dim) mat = voxel_material(q.scene, x, y, z);
+        } else if (x >= 0 && y >= 0 && z >= 0 && x < q.scene.map_dim[0] && y < q.scene.map_dim[1] && z < q.scene.map_dim[2]) {
+            const uint64_t idx = (uint64_t)((int64_t)x + (int64_t)q.scene.map_dim[0] * ((int64_t)y + (int64_t)q.scene.map_dim[2] * z));
+            mat = idx < q.scene.map_bytes ? (int)q.scene.map[idx] : 0;
         }
         q.values[i] = mat;
     }
@@ -170,23 +115,23 @@ __global__ __launch_bounds__(kReadThreads) void voxel_regions_kernel(const ReadP
         const int64_t ox = ((lo_x >> kReadBrickLog2) + jx) * kBrick, oy = ((lo_y >> kReadBrickLog2) + jy) * kBrick, oz = ((lo_z >> kReadBrickLog2) + jz) * kBrick;
         if (ox >= lo_x + sx || oy >= lo_y + sy || oz >= lo_z + sz) return;              // the brick misses its region
         uint64_t row = 0;
-        if (q.svo) {
-            const int n = q.log2_dim;
+        if (q.scene.svo) {
+            const int n = q.scene.log2_dim;
             const int64_t dim = (int64_t)1 << n;
             // (a brick wholly outside the map writes its zeros without touching the tree)
             if (ox >= 0 && oy >= 0 && oz >= 0 && ox < dim && oy < dim && oz < dim) {
                 if (n >= kReadBrickLog2) {
                     uint64_t cur = 0, index = 0;
-                    const int state = read_descend(q, (int)ox, (int)oy, (int)oz, kReadBrickLog2, cur, index);
+                    const int state = descend_to_node(q.scene, (int)ox, (int)oy, (int)oz, kReadBrickLog2, cur, index);
                     if (state == 1) row = 0x0505050505050505ULL;
-                    if (state == 2) row = resolve_row<3>(q, cur, index, ly, lz);
+                    if (state == 2) row = resolve_row<3>(q.scene, cur, index, ly, lz);
                 } else if (ly < dim && lz < dim) {
                     // a tree shallower than a brick: the brick at the origin holds the whole map, the rest of it is outside
-                    const uint64_t cur = read_entry(q.descriptors, q.root_index, q.descriptors[q.root_index]);
-                    row = n == 2 ? resolve_row<2>(q, cur, q.root_index, ly, lz) : resolve_row<1>(q, cur, q.root_index, ly, lz);
+                    const uint64_t cur = node_entry(q.scene.descriptors, q.scene.root_index, q.scene.descriptors[q.scene.root_index]);
+                    row = n == 2 ? resolve_row<2>(q.scene, cur, q.scene.root_index, ly, lz) : resolve_row<1>(q.scene, cur, q.scene.root_index, ly, lz);
                 }
             }
-        } else if (ox + kBrick > 0 && oy + kBrick > 0 && oz + kBrick > 0 && ox < q.map_dim[0] && oy < q.map_dim[1] && oz < q.map_dim[2]) {
+        } else if (ox + kBrick > 0 && oy + kBrick > 0 && oz + kBrick > 0 && ox < q.scene.map_dim[0] && oy < q.scene.map_dim[1] && oz < q.scene.map_dim[2]) {
             row = array_row(q, ox, oy + ly, oz + lz);
         }
         // the part of the row inside the region

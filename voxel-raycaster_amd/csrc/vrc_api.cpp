@@ -256,11 +256,10 @@ std::shared_ptr<vrc_tree> new_tree(int device, uint64_t *d_desc = nullptr, uint6
     t->device = device; t->d_desc = d_desc; t->n_desc = n_desc;
     return t;
 }
-// materials are bound as a pair or not at all (the parameter structs name the two fields alike); the caller holds t->guard
-template <class P>
-void bind_attachments(const vrc_tree *t, P &p) {
-    p.attach_lookup = (t->d_attach_lookup && t->d_attach) ? t->d_attach_lookup : nullptr;
-    p.attachments = p.attach_lookup ? t->d_attach : nullptr;
+// materials are bound as a pair or not at all (the frame's RaycastParams and the queries' SceneView); the caller holds t->guard
+void bind_attachments(const vrc_tree *t, const uint32_t *&attach_lookup, const uint64_t *&attachments) {
+    attach_lookup = (t->d_attach_lookup && t->d_attach) ? t->d_attach_lookup : nullptr;
+    attachments = attach_lookup ? t->d_attach : nullptr;
 }
 
 int prepare_one(vrc_caster *h);           // (below, beside the launch path that shares derive_from_tree with it)
@@ -1236,7 +1235,7 @@ int compute_async_one(vrc_caster *h) {
     p.atlas = h->d_atlas; p.atlas_w = h->atlas_w; p.atlas_h = h->atlas_h;
     p.tiles_x = h->atlas_w / h->tile_w; p.tiles_y = h->atlas_h / h->tile_h;
     p.descriptors = t->d_desc;
-    bind_attachments(t, p);
+    bind_attachments(t, p.attach_lookup, p.attachments);
     p.root_index = (uint64_t)root;
     // live buffers are re-read every frame (CL_MEM_USE_HOST_PTR semantics)
     for (int a = 0; a < 3; a++) p.cam_pos[a] = h->cam_pos[a];
@@ -1735,17 +1734,16 @@ bool boxes_for(const vrc_tree *t, uint64_t root, int n) {
     return coarse_for(t, root, n) && t->d_boxes && t->d_box_aux && t->boxes.built.at == t->coarse.built;
 }
 
-// The scene a ray or a box query runs against: the fields QueryParams and BoxParams name alike, from the handle's settings and its
+// The scene a query runs against (the SceneView of QueryParams, BoxParams and ReadParams), from the handle's settings and its
 // tree.  The caller holds t->guard.
-template <class P>
-void bind_scene(const vrc_caster *h, const vrc_tree *t, P &q) {
+void bind_scene(const vrc_caster *h, const vrc_tree *t, vrc::SceneView &q) {
     q.svo = setting_or(h, "using_octree", 0) == 0 ? 1 : 0;
     q.descriptors = t->d_desc;
     q.root_index = (uint64_t)setting_or(h, "octree_root_index", 0);
     q.log2_dim = log2_exact(setting_or(h, "octree_dimensions", 0));
     if (q.svo) {
         q.map_dim[0] = q.map_dim[1] = q.map_dim[2] = 1 << q.log2_dim;
-        bind_attachments(t, q);
+        bind_attachments(t, q.attach_lookup, q.attachments);
         if (setting_or(h, "coarse_log2", -1) != 0 && coarse_for(t, q.root_index, q.log2_dim)) { q.coarse = t->d_coarse; q.coarse_log2 = t->coarse.built.log2; }
     } else {
         for (int a = 0; a < 3; a++) q.map_dim[a] = h->map_dim[a];
@@ -1763,11 +1761,11 @@ int query_enqueue(vrc_caster *h, const float *d_rays, int64_t n, int32_t max_ste
     memset(&q, 0, sizeof(q));
     q.rays = d_rays; q.out = d_out; q.n = n; q.flags = flags;
     q.octree_bias = (int32_t)setting_or(h, "octree_bias", 1);
-    bind_scene(h, t, q);
+    bind_scene(h, t, q.scene);
     // max_steps = 0: no cap below the map's edge -- every iteration steps an axis, so 3 dim + 3 bounds a ray that starts inside
-    const int64_t dim_max = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
+    const int64_t dim_max = std::max(q.scene.map_dim[0], std::max(q.scene.map_dim[1], q.scene.map_dim[2]));
     q.cap = max_steps > 0 ? max_steps : (int32_t)std::min<int64_t>(INT32_MAX, 3 * dim_max + 3);
-    if (q.coarse && setting_or(h, "empty_boxes", -1) != 0 && boxes_for(t, q.root_index, q.log2_dim)) {
+    if (q.scene.coarse && setting_or(h, "empty_boxes", -1) != 0 && boxes_for(t, q.scene.root_index, q.scene.log2_dim)) {
         q.boxes = t->d_boxes; q.box_aux = t->d_box_aux; q.box_child = t->d_box_child; q.box_levels = t->box_levels;
     }
     HIP_TRY(h, vrc::launch_raycast_query(q, h->stream));
@@ -1835,7 +1833,7 @@ int box_passes(vrc_caster *h, vrc::BoxParams &q) {
     const int64_t n = q.n;
     const int32_t max_voxels = q.max_voxels;
     // the aligned space the items tile: the tree's, or the map's largest side rounded up
-    const int32_t side = std::max(q.map_dim[0], std::max(q.map_dim[1], q.map_dim[2]));
+    const int32_t side = std::max(q.scene.map_dim[0], std::max(q.scene.map_dim[1], q.scene.map_dim[2]));
     q.space_log2 = 1;
     while ((1 << q.space_log2) < side) q.space_log2++;
     // per-box scratch: plan, the two item counts and their scans, the totals, the corners
@@ -1887,7 +1885,7 @@ int box_enqueue(vrc_caster *h, const float *d_boxes, int64_t n, int32_t max_voxe
     memset(&q, 0, sizeof(q));
     q.boxes = d_boxes; q.box_stride = 6; q.n = n; q.max_voxels = max_voxels; q.flags = flags;
     q.records = d_rec; q.counts = d_cnt; q.voxels = max_voxels > 0 ? d_vox : nullptr;
-    bind_scene(h, h->tree.get(), q);
+    bind_scene(h, h->tree.get(), q.scene);
     return box_passes(h, q);
 }
 
@@ -1966,9 +1964,9 @@ int sweep_enqueue(vrc_caster *h, const float *d_sweeps, int64_t n, int32_t max_e
     q.boxes = d_sweeps; q.box_stride = 9; q.n = n; q.max_voxels = 1;
     q.flags = (flags & VRC_SWEEP_STOPPING_ONLY) ? vrc::kBoxStoppingOnly : 0u;
     q.records = h->d_sweep_rec; q.counts = h->d_sweep_cnt; q.voxels = h->d_sweep_vox;
-    bind_scene(h, h->tree.get(), q);
+    bind_scene(h, h->tree.get(), q.scene);
     p.records = d_rec;
-    const int64_t dims = (int64_t)q.map_dim[0] + q.map_dim[1] + q.map_dim[2];
+    const int64_t dims = (int64_t)q.scene.map_dim[0] + q.scene.map_dim[1] + q.scene.map_dim[2];
     p.cap = max_events > 0 ? max_events : (int32_t)std::min<int64_t>(INT32_MAX, 2 * dims + 64);
     p.lane_face_max = (int32_t)std::max<int64_t>(0, std::min<int64_t>(INT32_MAX, setting_or(h, "sweep_lane_face", vrc::kSweepLaneFaceMax)));
     int64_t *big_cnt = h->d_sweep_scan, *big_end = h->d_sweep_scan + n;
@@ -2052,7 +2050,7 @@ int read_enqueue(vrc_caster *h, const int32_t *d_in, int64_t n, const int32_t si
     vrc::ReadParams q;
     memset(&q, 0, sizeof(q));
     q.positions = d_in; q.n = n;
-    bind_scene(h, h->tree.get(), q);
+    bind_scene(h, h->tree.get(), q.scene);
     if (!size) {
         q.values = static_cast<int32_t *>(d_out);
         HIP_TRY(h, vrc::launch_voxel_points(q, h->stream));

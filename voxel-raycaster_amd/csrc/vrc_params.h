@@ -100,6 +100,22 @@ inline uint64_t coarse_index(unsigned cx, unsigned cy, unsigned cz, int lc) {
 // WITH boxes 3.16 instead of 2.40
 constexpr int coarse_level_for_depth(int n) { return n >= 14 ? kCoarseMaxLog2 + 1 : n >= 5 ? (n - 2 < kCoarseMaxLog2 ? n - 2 : kCoarseMaxLog2) : 0; }
 
+// The resident scene as the query kernels see it (QueryParams, BoxParams, ReadParams embed one; RaycastParams, the frame
+// kernels' block, keeps its own fields).  The host layer fills it in one place (bind_scene / bind_attachments, vrc_api.cpp).
+struct SceneView {
+    int32_t svo;                      // using_octree == 0: the tree; else the dense char map
+    const int8_t *map;                // array branch
+    int32_t map_dim[3];
+    uint64_t map_bytes;
+    const uint64_t *descriptors;      // the tree (svo_node.hpp)
+    uint64_t root_index;
+    int32_t log2_dim;
+    const uint32_t *attach_lookup;    // materials (optional, SVO branch): per-descriptor slot into attachments
+    const uint64_t *attachments;      // 8 int8 materials per bottom-level descriptor
+    const uint64_t *coarse;           // the tree's top as a dense table (nullptr: descend from the root)
+    int32_t coarse_log2;
+};
+
 // hit-record flag bits (include/vrc.h VRC_HIT_FLAG_*)
 constexpr int kFlagWritten = 1, kFlagShadowCast = 2, kFlagShadowHit = 4, kFlagOob = 8;
 constexpr int kFlagHasHit = 0x800;     // internal: the primary hit has been recorded (bits above 7 never leave the kernels)
