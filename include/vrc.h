@@ -494,6 +494,75 @@ int vrc_get_voxels_device(vrc_caster *h, const void *d_positions, int64_t n, voi
 int vrc_read_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], int8_t *out, size_t n_bytes);
 int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], void *d_out, size_t n_bytes);
 
+/* ---- voxel edits ---------------------------------------------------------- */
+
+/* Change the scene.  Map::setVoxel / ArrayMap::setVoxel (include/map/Map.h:42, ArrayMap.h:17) as a batch against the scene the
+ * handle renders: dig a hole, place a block, without reading the scene back and building it again -- which is a PCIe round trip
+ * of the whole grid, ends at depth 12 and does not exist for the trees that live only in HBM (vrc_build_shell_terrain,
+ * vrc_build_heightfield).
+ *
+ * positions int32[3 n], materials int32[n], each in [-128, 127]: the int8 vrc_get_voxels sign-extends; 0 clears the voxel.
+ * After the call vrc_get_voxels / vrc_read_regions return what applying the edits IN INDEX ORDER to the scene before the call
+ * gives: the highest index wins a position that occurs more than once.  An edit outside the scene -- [0, dim)^3 for the tree;
+ * map_dim, or an index past the array, for the map -- is ignored and counted in `skipped`.  Which scene is edited follows
+ * using_octree, as for the queries; a host that keeps both scenes makes two calls.  flags must be 0.  info may be NULL; set
+ * info->struct_size = sizeof(vrc_edit_info) before the call (never more than that is written).
+ *
+ * Array branch: a scatter into the map at the frame's index x + dx * (y + dz * z).
+ *
+ * SVO branch: a path-copying, APPEND-ONLY edit.  Every touched brick (a map-aligned cube of min(8, dim) voxels) is read, changed
+ * and rebuilt by one wave, every touched node above the bricks gets a new child block whose untouched children point, by far
+ * pointers, into the old array, and a new root word is appended; the last step moves n_descriptors and the octree_root_index
+ * setting of the handle (and of every rank of its group).  The edited tree is the tree vrc_build_dense_grid(...,
+ * VRC_BUILD_ATTACHMENTS) builds from the edited grid, up to layout: the same node at every position, the same (valid, leaf)
+ * masks, empty subtrees pruned up to the root (an empty scene is a root with valid mask 0), solid regions never collapsed into
+ * leaves; a solid leaf above the bottom level that is dug into becomes an ordinary node whose untouched children are leaves.
+ * Images, hit records and canonical read counts equal those of the rebuilt tree.
+ *   - Placement is a function of (array before the call, batch) alone: two handles with equal arrays that receive the same batch
+ *     end with bit-identical arrays.
+ *   - Growth: descriptors_added <= 72 * bricks_touched + 16 * (touched nodes above the bricks) + 1; words of the appended range
+ *     that hold nothing are zero.  Old words are never overwritten, so every edit leaves garbage behind and the array only
+ *     grows; there is no compaction.  The remedy is a rebuild: vrc_read_regions + vrc_build_dense_grid where the scene fits
+ *     that route, building the scene again otherwise.
+ *   - A batch that changes no voxel (voxels_changed == 0) appends nothing and leaves the root where it was.
+ *   - Materials: every rebuilt bottom-level descriptor gets an attachment slot of its own.  A tree without attachments stays
+ *     without them while every written material is 0 or 5 (trees that live only in HBM must not suddenly need 4 bytes per
+ *     descriptor); the first other material creates the lookup (all zeros) and slot 0 = eight 5s, and failing to allocate them is
+ *     VRC_ERR_OUT_OF_MEMORY with nothing changed.
+ *   - Capacity: when the batch does not fit what is allocated, the arrays are allocated anew with `edit_reserve` words to spare
+ *     and copied device to device (old and new exist side by side for that moment).  Setting edit_reserve: -1 (default) = an
+ *     eighth of the new size, at least 4096 words and at most a sixteenth of the free device memory; 0 = exact; n = n words.
+ *     vrc_octree_size and vrc_read_descriptors report n_descriptors; vrc_memory_usage*'s octree_bytes reports what is allocated.
+ *   - The coarse table and the empty boxes describe the old tree and are dropped; vrc_prepare, vrc_validate or the next
+ *     vrc_compute that finds them missing builds them again (about 15 ms for the table, 0.6 s for the boxes at depth 12).
+ *     Queries never start such a build and give the same results without them.  A host that edits every frame sets
+ *     empty_boxes = 0.
+ *   - A group handle replicates the call: ranks that share rank 0's tree only take the new root, ranks with their own copy run
+ *     the same edit on their GPU.  A tree that is also held by a handle OUTSIDE the caller's group (vrc_assign_octree_from)
+ *     is refused with VRC_ERR_LIMIT and nothing changes: that holder's octree_root_index cannot be moved from here.
+ *
+ * Host rules as vrc_box_intersection: synchronous on the handle's stream (a frame in flight finishes first); the image, hit
+ * records, counters, timing and vrc_last_kernel are untouched; the caller's device is restored; staging and scratch grow on
+ * demand and are freed by vrc_release_map / _octree / _viewport and vrc_destroy.  The _device variant takes memory the handle's
+ * GPU can read, 4-byte aligned, and waits for the null stream first; it cannot check the materials without a read-back, so an
+ * out-of-range material there makes that edit `skipped`.
+ * Errors, with nothing launched and nothing changed: VRC_ERR_INVALID_ARGUMENT for a null handle or pointer, n < 0, flags != 0,
+ * a misaligned device pointer, an info whose struct_size is below 4 or (host call) a material outside [-128, 127]; VRC_ERR_LIMIT for n > 2^31 - 1; VRC_ERR_NOT_READY
+ * as for ray queries.  n = 0 succeeds and changes nothing.  The edit is atomic: on any failure, VRC_ERR_OUT_OF_MEMORY while
+ * growing the arrays included, the scene, n_descriptors and the root are what they were.                                      */
+typedef struct vrc_edit_info {          /* size-versioned like vrc_memory2 */
+    uint32_t struct_size;               /* in: sizeof the caller's struct; out: bytes written */
+    uint32_t reserved_;
+    int64_t  skipped;                   /* edits outside the scene (ignored) */
+    int64_t  voxels_changed;            /* voxels whose material differs after the batch */
+    int64_t  bricks_touched;            /* SVO branch: map-aligned bricks rewritten; array branch: 0 */
+    uint64_t descriptors_added;         /* words the array grew by (descriptors, far slots and filler) */
+    uint64_t n_descriptors, root_index; /* the tree after the edit (SVO branch) */
+    double   seconds;                   /* device time of the edit's kernels */
+} vrc_edit_info;
+int vrc_set_voxels(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+
 /* Device pointers of the resident frame buffers (float4[w*h], int32[8*w*h]);
  * lets a host that owns the GPU (e.g. a torch process) consume the frame
  * without a PCIe round trip.                                                 */
@@ -676,6 +745,10 @@ int vrc_octree_generate_ex(const int8_t *grid, uint32_t dim, uint32_t layout, ui
 /* Read descriptors [first, first + count) of the resident octree back to the host (tests, tools). */
 int vrc_read_descriptors(vrc_caster *h, uint64_t first, uint64_t count, uint64_t *out);
 int vrc_octree_size(vrc_caster *h, uint64_t *n_descriptors, uint64_t *root_index);
+/* The materials of the resident octree, in the form vrc_assign_octree_attachments takes (tests, tools: an edited tree's exist only
+ * on the device): *n_attachments receives the number of slots, 0 for a tree without materials; lookup (uint32[n_descriptors])
+ * and attachments (uint64[capacity >= *n_attachments]) are filled where they are given.                                      */
+int vrc_read_attachments(vrc_caster *h, uint32_t *lookup, uint64_t *attachments, uint64_t capacity, uint64_t *n_attachments);
 
 /* Synthetic 256x256-style atlas: texel = hash(x,y) & 0xFFFFFF, alpha 255.    */
 int vrc_scene_atlas(int32_t width, int32_t height, uint8_t *rgba8);

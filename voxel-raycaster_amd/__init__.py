@@ -90,6 +90,15 @@ class KernelInfo(C.Structure):
                 ("jump_min_run", C.c_int32), ("lds_rows", C.c_int32), ("reserved_", C.c_int32), ("name", C.c_char * 96)]
 
 
+class EditInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("skipped", C.c_int64), ("voxels_changed", C.c_int64),
+                ("bricks_touched", C.c_int64), ("descriptors_added", C.c_uint64), ("n_descriptors", C.c_uint64), ("root_index", C.c_uint64),
+                ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved_")}
+
+
 class IndexAuditEntry(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in ("accesses", "max_index", "extent", "violations")] + [("first_index", C.c_int64), ("first_extent", C.c_uint64)]
                 + [(n, C.c_uint32) for n in ("first_block", "first_site", "extent_published", "reserved_")])
@@ -182,6 +191,7 @@ SIGNATURES = {
                                           _i32p, C.POINTER(BuildInfo)]),
     "vrc_read_descriptors": (C.c_int, [_H, C.c_uint64, C.c_uint64, _u64p]),
     "vrc_octree_size": (C.c_int, [_H, _u64p, _u64p]),
+    "vrc_read_attachments": (C.c_int, [_H, C.POINTER(C.c_uint32), _u64p, C.c_uint64, _u64p]),
     "vrc_cast_rays": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p]),
     "vrc_cast_rays_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p]),
     "vrc_box_intersection": (C.c_int, [_H, _f32p, C.c_int64, C.c_int32, C.c_uint32, _i32p, C.POINTER(C.c_int64), _i32p]),
@@ -192,6 +202,8 @@ SIGNATURES = {
     "vrc_get_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
     "vrc_read_regions": (C.c_int, [_H, _i32p, C.c_int64, _i32p, C.POINTER(C.c_int8), C.c_size_t]),
     "vrc_read_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),
+    "vrc_set_voxels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_set_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
@@ -618,6 +630,19 @@ class CLCaster:
             raise VrcError(self.last_error())
         return out
 
+    def read_attachments(self):
+        """vrc_read_attachments: (lookup uint32[n_descriptors], attachments uint64[n]) of the resident octree, or (None, None)
+        for a tree without materials."""
+        n = C.c_uint64()
+        if not self._ok(lib.vrc_read_attachments(self._h, None, None, 0, C.byref(n))):
+            raise VrcError(self.last_error())
+        if n.value == 0:
+            return None, None
+        lookup, attach = np.empty(self.octree_size()[0], dtype=np.uint32), np.empty(n.value, dtype=np.uint64)
+        if not self._ok(lib.vrc_read_attachments(self._h, _ptr(lookup, C.POINTER(C.c_uint32)), _ptr(attach, _u64p), attach.size, None)):
+            raise VrcError(self.last_error())
+        return lookup, attach
+
     # -- scene
     def assign_map(self, map_: "Map | np.ndarray", dims=None) -> bool:
         if isinstance(map_, Map):
@@ -887,6 +912,34 @@ class CLCaster:
         if sz.shape != (3,):
             raise VrcError(f"read_regions_device: size must be three integers, got {size}")
         return self._ok(lib.vrc_read_regions_device(self._h, C.c_void_p(lo_ptr), int(n), _ptr(sz, _i32p), C.c_void_p(out_ptr), int(n_bytes)))
+
+    # -- voxel edits (vrc_set_voxels, include/vrc.h)
+    def set_voxels(self, positions: np.ndarray, materials) -> dict:
+        """Write materials (n,) into the voxels positions (n, 3) int32 of the scene using_octree selects, in index order (the
+        last edit of a position wins; 0 clears; outside the scene is skipped).  Returns vrc_edit_info as a dict: skipped,
+        voxels_changed, bricks_touched, descriptors_added, n_descriptors, root_index, seconds.  Raises on failure."""
+        p = np.ascontiguousarray(positions, dtype=np.int32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise VrcError(f"set_voxels: positions must have shape (n, 3), got {p.shape}")
+        m = np.asarray(materials)
+        if m.shape != (p.shape[0],):
+            raise VrcError(f"set_voxels: materials must have shape ({p.shape[0]},), got {m.shape}")
+        if m.size and (m.min() < -2 ** 31 or m.max() >= 2 ** 31):
+            raise VrcError("set_voxels: a material does not fit int32")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        info = EditInfo()
+        info.struct_size = C.sizeof(EditInfo)
+        if not self._ok(lib.vrc_set_voxels(self._h, _ptr(p, _i32p), _ptr(m, _i32p), p.shape[0], 0, C.byref(info))):
+            raise VrcError(self.last_error())
+        return info.as_dict()
+
+    def set_voxels_device(self, positions_ptr: int, materials_ptr: int, n: int) -> dict:
+        """set_voxels on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 3 int32 and n int32)."""
+        info = EditInfo()
+        info.struct_size = C.sizeof(EditInfo)
+        if not self._ok(lib.vrc_set_voxels_device(self._h, C.c_void_p(positions_ptr), C.c_void_p(materials_ptr), int(n), 0, C.byref(info))):
+            raise VrcError(self.last_error())
+        return info.as_dict()
 
     def counters(self) -> dict:
         c = Counters()

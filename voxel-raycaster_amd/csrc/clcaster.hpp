@@ -170,6 +170,18 @@ public:
         return ok(vrc_read_regions_device(h_, d_lo, n, size, d_materials, n_bytes));
     }
 
+    // extension: Map::setVoxel (Map.h:42) as a batch against the resident scene (vrc_set_voxels): positions = 3 int32 each,
+    // materials = one int32 each in [-128, 127], applied in index order; info (optional) receives what the edit did
+    bool set_voxels(const std::vector<int32_t> &positions, const std::vector<int32_t> &materials, vrc_edit_info *info = nullptr) {
+        if (positions.size() != 3 * materials.size()) return ok(VRC_ERR_INVALID_ARGUMENT);
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_set_voxels(h_, positions.data(), materials.data(), (int64_t)materials.size(), 0u, info));
+    }
+    bool set_voxels_device(const void *d_positions, const void *d_materials, int64_t n, vrc_edit_info *info = nullptr) {
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_set_voxels_device(h_, d_positions, d_materials, n, 0u, info));
+    }
+
     int last_status() const { return status_; }
     std::string last_error() const { return h_ ? vrc_last_error(h_) : "not initialised"; }
     vrc_caster *handle() { return h_; }

@@ -137,6 +137,39 @@ VRC_NODE_WALK int voxel_material(const SceneView &s, int x, int y, int z) {
     return state == 1 ? 5 : 0;
 }
 
+// The 2^kLevel voxels along x of row (y, z) of the node `cur` (at `index`, of size 2^kLevel, kLevel <= 3), one byte each, lowest
+// x first: the unit of the region read (voxel_read.hip) and of the edit's brick pass (voxel_edit.hip), a lane per row.
+template <int kLevel>
+VRC_NODE_FN uint64_t node_row(const SceneView &s, uint64_t cur, uint64_t index, int y, int z) {
+    constexpr int cb = kLevel - 1;                        // the children are 2^cb voxels wide
+    const int yz = (((y >> cb) & 1) << 1) | (((z >> cb) & 1) << 2);
+    const unsigned masks = (unsigned)cur & 0xffffu;
+    uint64_t row = 0;
+    if constexpr (kLevel == 1) {
+        if (masks & (3u << yz)) {
+            const uint64_t mats = bottom_materials(s, index);
+            for (int h = 0; h < 2; h++)
+                if (masks & (1u << (yz | h))) row |= ((mats >> (8 * (yz | h))) & 0xffULL) << (8 * h);
+        }
+    } else {
+        constexpr uint64_t solid = 0x0505050505050505ULL >> (64 - 8 * (1 << cb));       // 2^cb bytes of 5
+        for (int h = 0; h < 2; h++) {
+            const unsigned bit = 1u << (yz | h);
+            uint64_t half = 0;
+            if (masks & bit) {
+                if ((masks >> 8) & bit) {
+                    half = solid;
+                } else {
+                    const uint64_t child = kept_child(cur, (unsigned)(yz | h));
+                    half = node_row<kLevel - 1>(s, node_entry(s.descriptors, child, s.descriptors[VRC_IDX(kDescriptors, child)]), child, y, z);
+                }
+            }
+            row |= half << (8 * h * (1 << cb));
+        }
+    }
+    return row;
+}
+
 // An empty-box word (empty_boxes.hip) holds six 5-bit extent codes, in units of the node's size: the extent of code c
 VRC_NODE_FN int box_extent(unsigned c) { return c < 4u ? (int)c : (int)((4u | (c & 3u)) << ((c >> 2) - 1u)); }
 

@@ -25,38 +25,6 @@ namespace vrc {
 
 namespace {
 
-// The 2^kLevel voxels along x of row (y, z) of the node `cur` (at `index`, of size 2^kLevel), one byte each, lowest x first.
-template <int kLevel>
-__device__ __forceinline__ uint64_t resolve_row(const SceneView &s, uint64_t cur, uint64_t index, int y, int z) {
-    constexpr int cb = kLevel - 1;                        // the children are 2^cb voxels wide
-    const int yz = (((y >> cb) & 1) << 1) | (((z >> cb) & 1) << 2);
-    const unsigned masks = (unsigned)cur & 0xffffu;
-    uint64_t row = 0;
-    if constexpr (kLevel == 1) {
-        if (masks & (3u << yz)) {
-            const uint64_t mats = bottom_materials(s, index);
-            for (int h = 0; h < 2; h++)
-                if (masks & (1u << (yz | h))) row |= ((mats >> (8 * (yz | h))) & 0xffULL) << (8 * h);
-        }
-    } else {
-        constexpr uint64_t solid = 0x0505050505050505ULL >> (64 - 8 * (1 << cb));       // 2^cb bytes of 5
-        for (int h = 0; h < 2; h++) {
-            const unsigned bit = 1u << (yz | h);
-            uint64_t half = 0;
-            if (masks & bit) {
-                if ((masks >> 8) & bit) {
-                    half = solid;
-                } else {
-                    const uint64_t child = kept_child(cur, (unsigned)(yz | h));
-                    half = resolve_row<kLevel - 1>(s, node_entry(s.descriptors, child, s.descriptors[VRC_IDX(kDescriptors, child)]), child, y, z);
-                }
-            }
-            row |= half << (8 * h * (1 << cb));
-        }
-    }
-    return row;
-}
-
 // array branch: voxels (x .. x + 7, y, z) by the frame's index (y stride map_dim[2]); past the array and outside map_dim reads as 0
 __device__ __forceinline__ uint64_t array_row(const ReadParams &q, int64_t x, int64_t y, int64_t z) {
     if (y < 0 || y >= q.scene.map_dim[1] || z < 0 || z >= q.scene.map_dim[2]) return 0;
@@ -124,11 +92,11 @@ __global__ __launch_bounds__(kReadThreads) void voxel_regions_kernel(const ReadP
                     uint64_t cur = 0, index = 0;
                     const int state = descend_to_node(q.scene, (int)ox, (int)oy, (int)oz, kReadBrickLog2, cur, index);
                     if (state == 1) row = 0x0505050505050505ULL;
-                    if (state == 2) row = resolve_row<3>(q.scene, cur, index, ly, lz);
+                    if (state == 2) row = node_row<3>(q.scene, cur, index, ly, lz);
                 } else if (ly < dim && lz < dim) {
                     // a tree shallower than a brick: the brick at the origin holds the whole map, the rest of it is outside
                     const uint64_t cur = node_entry(q.scene.descriptors, q.scene.root_index, q.scene.descriptors[VRC_IDX(kDescriptors, q.scene.root_index)]);
-                    row = n == 2 ? resolve_row<2>(q.scene, cur, q.scene.root_index, ly, lz) : resolve_row<1>(q.scene, cur, q.scene.root_index, ly, lz);
+                    row = n == 2 ? node_row<2>(q.scene, cur, q.scene.root_index, ly, lz) : node_row<1>(q.scene, cur, q.scene.root_index, ly, lz);
                 }
             }
         } else if (ox + kBrick > 0 && oy + kBrick > 0 && oz + kBrick > 0 && ox < q.scene.map_dim[0] && oy < q.scene.map_dim[1] && oz < q.scene.map_dim[2]) {

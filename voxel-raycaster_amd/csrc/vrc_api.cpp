@@ -27,6 +27,7 @@
 #include "box_query.h"
 #include "box_sweep.h"
 #include "raycast_query.h"
+#include "voxel_edit.h"
 #include "voxel_read.h"
 #include "vrc_launch.h"
 #include "vrc_params.h"
@@ -35,7 +36,7 @@
 #include "index_audit.hpp"
 namespace vrc {
 #define VRC_AUDIT_DECLARE(name) hipError_t audit_publish_##name(const unsigned long long *extent_plus_1); hipError_t audit_collect_##name(audit::Stat *out, unsigned long long *extent_plus_1, int clear);
-VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read)
+VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit)
 #undef VRC_AUDIT_DECLARE
 }  // namespace vrc
 #endif
@@ -88,6 +89,11 @@ struct vrc_tree {
     int device = 0;
     uint64_t *d_desc = nullptr; uint64_t n_desc = 0;
     uint32_t *d_attach_lookup = nullptr; uint64_t *d_attach = nullptr; uint64_t n_attach = 0;
+    // words allocated, once an edit (vrc_set_voxels) has grown an array beyond what it holds; 0: exactly what it holds
+    uint64_t cap_desc = 0, cap_lookup = 0, cap_attach = 0;
+    uint64_t desc_capacity() const { return cap_desc ? cap_desc : n_desc; }
+    uint64_t lookup_capacity() const { return cap_lookup ? cap_lookup : n_desc; }
+    uint64_t attach_capacity() const { return cap_attach ? cap_attach : std::max<uint64_t>(n_attach, 1); }
     // derived, built on first use by whichever handle needs them first (guard: handles of several host threads)
     std::mutex guard;
     uint64_t *d_coarse = nullptr; Derived<TableKey> coarse;
@@ -149,6 +155,14 @@ struct vrc_caster {
     // vrc_get_voxels / vrc_read_regions: staging of the host calls (positions or corners in, values or bytes out)
     int32_t *d_read_in = nullptr; int64_t read_in_capacity = 0;
     void *d_read_out = nullptr; size_t read_out_bytes = 0;
+    // vrc_set_voxels: staging of the host call (positions, materials); keys and edit numbers (unsorted, sorted), the unique keys
+    // and their run lengths; the counters; rocprim's storage; the touched nodes above the bricks (keys) and every touched node's record
+    int32_t *d_edit_in = nullptr; int64_t edit_in_capacity = 0;
+    uint64_t *d_edit_keys = nullptr, *d_edit_unique = nullptr; uint32_t *d_edit_order = nullptr, *d_edit_counts = nullptr; int64_t edit_capacity = 0;
+    unsigned long long *d_edit_counters = nullptr;
+    void *d_edit_temp = nullptr; size_t edit_temp_bytes = 0;
+    uint64_t *d_edit_levels = nullptr; int64_t edit_level_capacity = 0;
+    uint32_t *d_edit_rec_masks = nullptr; uint64_t *d_edit_rec_child = nullptr; int64_t edit_rec_capacity = 0;
 
     // live (retained) host pointers
     const float *cam_dir = nullptr, *cam_pos = nullptr;
@@ -212,11 +226,12 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
         }                                                                                         \
     } while (0)
 
-// vrc_cast_rays', vrc_box_intersection's, vrc_sweep_boxes' and the voxel reads' staging and scratch buffers (the caller's device is left
+// vrc_cast_rays', vrc_box_intersection's, vrc_sweep_boxes', the voxel reads' and the voxel edits' staging and scratch buffers (the caller's device is left
 // as it was)
 void release_query_staging(vrc_caster *h) {
     if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp &&
-        !h->d_sweep_in && !h->d_sweep_rec && !h->d_read_in && !h->d_read_out) return;
+        !h->d_sweep_in && !h->d_sweep_rec && !h->d_read_in && !h->d_read_out && !h->d_edit_in && !h->d_edit_keys && !h->d_edit_counters &&
+        !h->d_edit_temp && !h->d_edit_levels && !h->d_edit_rec_masks) return;
     {
         DeviceRestore restore;
         (void)hipSetDevice(h->device);
@@ -229,6 +244,9 @@ void release_query_staging(vrc_caster *h) {
         h->sweep_io_capacity = 0; h->sweep_capacity = 0;
         release(h->d_read_in); release(h->d_read_out);
         h->read_in_capacity = 0; h->read_out_bytes = 0;
+        release(h->d_edit_in); release(h->d_edit_keys); release(h->d_edit_unique); release(h->d_edit_order); release(h->d_edit_counts);
+        release(h->d_edit_counters); release(h->d_edit_temp); release(h->d_edit_levels); release(h->d_edit_rec_masks); release(h->d_edit_rec_child);
+        h->edit_in_capacity = 0; h->edit_capacity = 0; h->edit_temp_bytes = 0; h->edit_level_capacity = 0; h->edit_rec_capacity = 0;
     }
     (void)hipGetLastError();
 }
@@ -294,7 +312,7 @@ const AuditTu kAuditTus[] = {
     {vrc::audit_publish_raycast, vrc::audit_collect_raycast}, {vrc::audit_publish_jump, vrc::audit_collect_jump},
     {vrc::audit_publish_boxes, vrc::audit_collect_boxes},     {vrc::audit_publish_query, vrc::audit_collect_query},
     {vrc::audit_publish_boxq, vrc::audit_collect_boxq},       {vrc::audit_publish_sweep, vrc::audit_collect_sweep},
-    {vrc::audit_publish_read, vrc::audit_collect_read},
+    {vrc::audit_publish_read, vrc::audit_collect_read},       {vrc::audit_publish_edit, vrc::audit_collect_edit},
 };
 hipError_t audit_publish(const AuditExtents &x) {
     hipError_t e = hipDeviceSynchronize();
@@ -768,6 +786,7 @@ int vrc_assign_octree_attachments(vrc_caster *h, const uint32_t *lookup, uint64_
         if (t) {
             std::lock_guard<std::mutex> lock(t->guard);            // (another holder's frame reads these pointers under the guard)
             (void)hipSetDevice(t->device); release(t->d_attach_lookup); release(t->d_attach); t->n_attach = 0;
+            t->cap_lookup = t->cap_attach = 0;
         }
         q->validated = false;
     };
@@ -940,6 +959,25 @@ int vrc_read_descriptors(vrc_caster *h, uint64_t first, uint64_t count, uint64_t
     if (first > h->tree->n_desc || count > h->tree->n_desc - first) return fail(h, VRC_ERR_INVALID_ARGUMENT, "read_descriptors: range past the array");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpy(out, h->tree->d_desc + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VRC_OK;
+}
+
+// the materials of the resident octree, as vrc_assign_octree_attachments takes them (tests, tools: an edited tree's are made on the device)
+int vrc_read_attachments(vrc_caster *h, uint32_t *lookup, uint64_t *attachments, uint64_t capacity, uint64_t *n_attachments) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    vrc_tree *t = h->tree.get();
+    if (!t) return fail(h, VRC_ERR_NOT_READY, "read_attachments: no octree assigned");
+    std::lock_guard<std::mutex> lock(t->guard);
+    const bool have = t->d_attach_lookup && t->d_attach;
+    const uint64_t n = have ? std::max<uint64_t>(t->n_attach, 1) : 0;
+    if (n_attachments) *n_attachments = n;
+    if (!have || (!lookup && !attachments)) return VRC_OK;
+    if (attachments && capacity < n) return fail(h, VRC_ERR_INVALID_ARGUMENT, "read_attachments: %llu slots, room for %llu", (unsigned long long)n, (unsigned long long)capacity);
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (lookup) HIP_TRY(h, hipMemcpy(lookup, t->d_attach_lookup, t->n_desc * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (attachments) HIP_TRY(h, hipMemcpy(attachments, t->d_attach, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VRC_OK;
 }
 
@@ -1622,7 +1660,8 @@ int vrc_memory_usage2(vrc_caster *h, int32_t rank, vrc_memory2 *out) {
     m.octree_shared = q->owns_desc ? 0 : 1;
     m.peer_access = q->peer_access;
     if (const vrc_tree *t = q->tree.get()) {
-        m.octree_bytes = t->n_desc * 8 + (t->d_attach_lookup ? t->n_desc * 4 + std::max<uint64_t>(t->n_attach, 1) * 8 : 0);
+        // (what is allocated: after an edit has grown the arrays, more than the n_desc words vrc_octree_size reports)
+        m.octree_bytes = t->desc_capacity() * 8 + (t->d_attach_lookup ? t->lookup_capacity() * 4 + t->attach_capacity() * 8 : 0);
         m.tree_holders = (int32_t)q->tree.use_count();
         m.coarse_log2 = t->d_coarse ? t->coarse.built.log2 : 0;
         m.coarse_bytes = t->d_coarse ? (uint64_t)sizeof(uint64_t) << (3 * t->coarse.built.log2) : 0;
@@ -2277,6 +2316,327 @@ int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const in
     int rc = region_check(h, d_lo, n, size, d_out, n_bytes, &total, "read_regions_device");
     if (rc != VRC_OK || n == 0) return rc;
     return read_device(h, d_lo, n, size, d_out, "read_regions_device");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// voxel edits (vrc_set_voxels / vrc_set_voxels_device, voxel_edit.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the argument checks of both calls, then the readiness checks of the ray queries; nothing is launched when one fails
+int edit_check(vrc_caster *h, const void *positions, const void *materials, int64_t n, uint32_t flags, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    if (flags) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)flags);
+    if (n > 0 && (!positions || !materials)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null positions or materials", what);
+    if (n > INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 edits in one batch", what);
+    VRC_TRY(query_check(h, positions, n, 0, 0, materials, what));
+    if (setting_or(h, "using_octree", 0) != 0) return VRC_OK;
+    // a holder of the tree outside this group would keep rendering from the old root: its setting cannot be moved from here
+    std::vector<const vrc_caster *> group{h};
+    group.insert(group.end(), h->peers.begin(), h->peers.end());
+    for (const vrc_caster *g : group) {
+        if (!g->tree) return fail(h, VRC_ERR_NOT_READY, "%s: a rank of the group has no octree", what);
+        long inside = 0;
+        for (const vrc_caster *o : group) inside += o->tree.get() == g->tree.get() ? 1 : 0;
+        if (g->tree.use_count() > inside)
+            return fail(h, VRC_ERR_LIMIT, "%s: the tree is also held by a handle outside this group (vrc_assign_octree_from); its root cannot be moved from here", what);
+    }
+    return VRC_OK;
+}
+
+// What one handle's edit has prepared and edit_commit installs.  Until then the tree is what it was: the appended words lie
+// behind n_desc, in the tree's own arrays where they had room and in the arrays staged here where they had not.
+struct EditStage {
+    vrc_caster *h = nullptr;
+    bool ran = false, commit = false;
+    int64_t skipped = 0, changed = 0, bricks = 0;
+    uint64_t added = 0, n_desc = 0, root = 0, n_attach = 0;
+    double seconds = 0.0;
+    uint64_t *desc = nullptr; uint32_t *lookup = nullptr; uint64_t *attach = nullptr;       // replace the tree's at the commit
+    uint64_t cap_desc = 0, cap_lookup = 0, cap_attach = 0;
+    EditStage() = default;
+    EditStage(const EditStage &) = delete;
+    EditStage &operator=(const EditStage &) = delete;
+    ~EditStage() {
+        if (!desc && !lookup && !attach) return;
+        DeviceRestore restore;
+        (void)hipSetDevice(h->device);
+        release(desc); release(lookup); release(attach);
+        (void)hipGetLastError();
+    }
+};
+
+// words to allocate beyond `need` when an array has to grow (setting edit_reserve; -1: an eighth of the need, at least 4096 words,
+// at most a sixteenth of the device memory that is free)
+uint64_t edit_reserve_for(const vrc_caster *h, uint64_t need, size_t elem_bytes, size_t free_bytes) {
+    const int64_t asked = setting_or(h, "edit_reserve", -1);
+    if (asked >= 0) return (uint64_t)asked;
+    return std::min<uint64_t>(std::max<uint64_t>(need / 8, 4096), (uint64_t)(free_bytes / 16) / elem_bytes);
+}
+
+// device time between two events of the handle's stream, added to *seconds (the stream has been waited for)
+struct EditTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EditTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipError_t init() { hipError_t e = hipEventCreate(&a); return e == hipSuccess ? hipEventCreate(&b) : e; }
+    void add(double *seconds) { float ms = 0.f; if (hipEventElapsedTime(&ms, a, b) == hipSuccess) *seconds += ms * 1e-3; else (void)hipGetLastError(); }
+};
+
+// One handle's edit up to the commit (current device: g->device; d_pos / d_mat: memory of that device).  The array branch
+// stores in place; the SVO branch appends behind n_desc and leaves the commit to the caller.
+int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_t n, EditStage &st) {
+    st.h = g; st.ran = true;
+    vrc_tree *t = g->tree.get();
+    std::unique_lock<std::mutex> lock(t->guard);
+    HIP_TRY(g, hipStreamSynchronize(g->stream));                      // a frame in flight finishes first
+    vrc::EditParams q;
+    memset(&q, 0, sizeof(q));
+    bind_scene(g, t, q.scene);
+    q.scene.coarse = nullptr; q.scene.coarse_log2 = 0;                // (the table goes with the edit: every descent starts at the root)
+    const bool svo = q.scene.svo != 0;
+    const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);   // levels above the bricks
+    int bits = 3 * above;
+    if (!svo)
+        for (bits = 0; bits < 63 && (1ULL << bits) <= q.scene.map_bytes; bits++) {}
+    q.sentinel = svo ? 1ULL << bits : q.scene.map_bytes;
+    q.positions = d_pos; q.materials = d_mat; q.n = n;
+    q.map = g->d_map;
+    VRC_TRY(grow(g, g->edit_capacity, n, {{g->d_edit_keys, sizeof(uint64_t) * 2 * (size_t)n}, {g->d_edit_order, sizeof(uint32_t) * 2 * (size_t)n},
+                                          {g->d_edit_unique, sizeof(uint64_t) * (size_t)n}, {g->d_edit_counts, sizeof(uint32_t) * (size_t)n}}));
+    if (!g->d_edit_counters) HIP_TRY(g, hipMalloc((void **)&g->d_edit_counters, sizeof(unsigned long long) * vrc::kEditCounters));
+    q.keys = g->d_edit_keys; q.order = g->d_edit_order;
+    q.sorted_keys = g->d_edit_keys + n; q.sorted_order = g->d_edit_order + n;
+    q.counters = g->d_edit_counters;
+    size_t sort_bytes = 0, run_bytes = 0;
+    HIP_TRY(g, vrc::edit_sort(nullptr, &sort_bytes, q.keys, g->d_edit_keys + n, q.order, g->d_edit_order + n, n, bits + 1, g->stream));
+    HIP_TRY(g, vrc::edit_runs(nullptr, &run_bytes, q.sorted_keys, n, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
+    const size_t temp_bytes = std::max<size_t>(std::max(sort_bytes, run_bytes), 16);
+    VRC_TRY(grow(g, g->edit_temp_bytes, temp_bytes, {{g->d_edit_temp, temp_bytes}}));
+    EditTimer timer;
+    HIP_TRY(g, timer.init());
+    unsigned long long c[vrc::kEditCounters];
+
+    HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(c), g->stream));
+    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
+    HIP_TRY(g, vrc::launch_edit_keys(q, g->stream));
+    HIP_TRY(g, vrc::edit_sort(g->d_edit_temp, &sort_bytes, q.keys, g->d_edit_keys + n, q.order, g->d_edit_order + n, n, bits + 1, g->stream));
+    if (svo) HIP_TRY(g, vrc::edit_runs(g->d_edit_temp, &run_bytes, q.sorted_keys, n, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
+    else HIP_TRY(g, vrc::launch_edit_array(q, g->stream));
+    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    timer.add(&st.seconds);
+    st.skipped = (int64_t)c[vrc::kEditSkipped];
+    if (!svo) { st.changed = (int64_t)c[vrc::kEditChanged]; return VRC_OK; }
+
+    // the touched bricks (the last run is the skipped edits'), and from their keys the touched nodes of every level above them
+    const int64_t nb = (int64_t)c[vrc::kEditRuns] - (st.skipped > 0 ? 1 : 0);
+    if (nb <= 0) return VRC_OK;
+    std::vector<std::vector<uint64_t>> levels((size_t)above);
+    {
+        std::vector<uint64_t> below((size_t)nb);
+        HIP_TRY(g, hipMemcpy(below.data(), g->d_edit_unique, sizeof(uint64_t) * (size_t)nb, hipMemcpyDeviceToHost));
+        for (int j = 0; j < above; j++) {
+            std::vector<uint64_t> &here = levels[(size_t)j];
+            for (uint64_t k : (j ? levels[(size_t)j - 1] : below))
+                if (here.empty() || here.back() != k >> 3) here.push_back(k >> 3);
+        }
+    }
+    int64_t ancestors = 0;
+    for (const auto &l : levels) ancestors += (int64_t)l.size();
+    // the appended range: [a root word in front of a depth-3 brick] the bricks, the levels from the bricks' parents up, the
+    // root word in front of the root level's block
+    const uint64_t first = t->n_desc;
+    st.added = vrc::kEditBrickStride * (uint64_t)nb + vrc::kEditNodeStride * (uint64_t)ancestors + (nlog >= vrc::kReadBrickLog2 ? 1 : 0);
+    st.bricks = nb;
+    st.n_desc = first + st.added;
+    q.brick_base = first + (nlog == vrc::kReadBrickLog2 ? 1 : 0);
+    st.root = above ? st.n_desc - vrc::kEditNodeStride - 1 : first;
+    const bool have = t->d_attach_lookup && t->d_attach, want = have || c[vrc::kEditMaterials] != 0;
+    q.attach_base = have ? std::max<uint64_t>(t->n_attach, 1) : 1;    // (a tree that gets its materials now: slot 0 is eight 5s)
+    st.n_attach = want ? q.attach_base + vrc::kEditBrickAttach * (uint64_t)nb : 0;
+    if (st.n_attach > 0xffffffffULL) return fail(g, VRC_ERR_LIMIT, "set_voxels: more than 2^32 attachment slots");
+    if (st.n_desc >= (1ULL << 47)) return fail(g, VRC_ERR_LIMIT, "set_voxels: more than 2^47 descriptors");
+
+    // room: arrays that cannot take the batch are staged anew and copied device to device; the tree keeps its own until the commit
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    auto staged = [&](auto *&p, uint64_t &cap, uint64_t need, size_t elem) -> hipError_t {
+        cap = need + edit_reserve_for(g, need, elem, free_b);
+        return hipMalloc((void **)&p, cap * elem);
+    };
+    hipError_t e = hipSuccess;
+    if (st.n_desc > t->desc_capacity()) {
+        e = staged(st.desc, st.cap_desc, st.n_desc, sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMemcpyAsync(st.desc, t->d_desc, first * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream);
+    }
+    if (e == hipSuccess && want && (!have || st.n_desc > t->lookup_capacity())) {
+        e = staged(st.lookup, st.cap_lookup, st.n_desc, sizeof(uint32_t));
+        if (e == hipSuccess) e = have ? hipMemcpyAsync(st.lookup, t->d_attach_lookup, first * sizeof(uint32_t), hipMemcpyDeviceToDevice, g->stream)
+                                      : hipMemsetAsync(st.lookup, 0, first * sizeof(uint32_t), g->stream);
+    }
+    if (e == hipSuccess && want && (!have || st.n_attach > t->attach_capacity())) {
+        e = staged(st.attach, st.cap_attach, st.n_attach, sizeof(uint64_t));
+        if (e == hipSuccess) e = have ? hipMemcpyAsync(st.attach, t->d_attach, q.attach_base * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream)
+                                      : hipMemsetAsync(st.attach, 0x05, sizeof(uint64_t), g->stream);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(g, e == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE, "set_voxels: growing the octree by %llu words failed: %s",
+                    (unsigned long long)st.added, hipGetErrorString(e));
+    }
+    q.descriptors = st.desc ? st.desc : t->d_desc;
+    q.attach_lookup = !want ? nullptr : st.lookup ? st.lookup : t->d_attach_lookup;
+    q.attachments = !want ? nullptr : st.attach ? st.attach : t->d_attach;
+    HIP_TRY(g, hipMemsetAsync(q.descriptors + first, 0, st.added * sizeof(uint64_t), g->stream));     // (what no pass stores stays zero)
+    if (want) {
+        HIP_TRY(g, hipMemsetAsync(q.attach_lookup + first, 0, st.added * sizeof(uint32_t), g->stream));
+        HIP_TRY(g, hipMemsetAsync(q.attachments + q.attach_base, 0, (st.n_attach - q.attach_base) * sizeof(uint64_t), g->stream));
+    }
+    VRC_TRY(grow(g, g->edit_rec_capacity, nb + ancestors, {{g->d_edit_rec_masks, sizeof(uint32_t) * (size_t)(nb + ancestors)},
+                                                           {g->d_edit_rec_child, sizeof(uint64_t) * (size_t)(nb + ancestors)}}));
+    if (ancestors) VRC_TRY(grow(g, g->edit_level_capacity, ancestors, {{g->d_edit_levels, sizeof(uint64_t) * (size_t)ancestors}}));
+    {
+        int64_t at = 0;
+        for (const auto &l : levels) {
+            HIP_TRY(g, hipMemcpyAsync(g->d_edit_levels + at, l.data(), sizeof(uint64_t) * l.size(), hipMemcpyHostToDevice, g->stream));
+            at += (int64_t)l.size();
+        }
+    }
+    q.brick_keys = g->d_edit_unique; q.n_bricks = nb;
+    q.rec_masks = g->d_edit_rec_masks; q.rec_child = g->d_edit_rec_child;
+    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
+    HIP_TRY(g, vrc::launch_edit_bricks(q, g->stream));
+    {
+        vrc::EditLevel l;
+        memset(&l, 0, sizeof(l));
+        l.below_keys = g->d_edit_unique; l.below_count = nb; l.rec_below = 0;
+        l.keys = g->d_edit_levels; l.rec_here = nb;
+        l.base = first + vrc::kEditBrickStride * (uint64_t)nb;
+        for (int j = 0; j < above; j++) {
+            l.count = (int64_t)levels[(size_t)j].size();
+            l.r = vrc::kReadBrickLog2 + 1 + j; l.root = j == above - 1 ? 1 : 0;
+            HIP_TRY(g, vrc::launch_edit_level(q, l, g->stream));
+            l.below_keys = l.keys; l.below_count = l.count; l.rec_below = l.rec_here;
+            l.keys += l.count; l.rec_here += l.count; l.base += vrc::kEditNodeStride * (uint64_t)l.count;
+        }
+    }
+    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    timer.add(&st.seconds);
+    st.changed = (int64_t)c[vrc::kEditChanged];
+    st.commit = st.changed != 0;              // a batch that changes no voxel appends nothing: the words behind n_desc are simply not taken
+    return VRC_OK;
+}
+
+// The last step: the staged arrays replace the tree's (the old ones are freed once the device is idle: hipFree waits), the
+// appended words are taken, what was derived from the old tree goes, and the handle's root moves.
+void edit_commit(EditStage &st) {
+    vrc_caster *g = st.h;
+    vrc_tree *t = g->tree.get();
+    std::lock_guard<std::mutex> lock(t->guard);
+    (void)hipSetDevice(g->device);
+    (void)hipStreamSynchronize(g->stream);
+    auto install = [](auto *&mine, auto *&staged, uint64_t &cap, uint64_t staged_cap) {
+        if (!staged) return;
+        auto *old = mine;
+        mine = staged; cap = staged_cap; staged = nullptr;
+        if (old) (void)hipFree(old);
+    };
+    install(t->d_desc, st.desc, t->cap_desc, st.cap_desc);
+    install(t->d_attach_lookup, st.lookup, t->cap_lookup, st.cap_lookup);
+    install(t->d_attach, st.attach, t->cap_attach, st.cap_attach);
+    if (!t->cap_desc) t->cap_desc = t->n_desc;                        // (the capacities are what is allocated, from here on)
+    if (t->d_attach_lookup && !t->cap_lookup) t->cap_lookup = t->n_desc;
+    if (t->d_attach && !t->cap_attach) t->cap_attach = std::max<uint64_t>(t->n_attach, 1);
+    t->n_desc = st.n_desc;
+    if (st.n_attach) t->n_attach = st.n_attach;
+    // the coarse table and the empty boxes describe the old tree: vrc_prepare / vrc_validate / the next frame build them again
+    release(t->d_coarse); t->coarse.built = TableKey{};
+    release_boxes(t);
+    (void)hipGetLastError();
+}
+
+int edit_run(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, bool on_device, vrc_edit_info *info, const char *what) {
+    if (info && info->struct_size < sizeof(uint32_t)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: info->struct_size is not set", what);
+    vrc_edit_info out;
+    memset(&out, 0, sizeof(out));
+    const bool svo = setting_or(h, "using_octree", 0) == 0;
+    DeviceRestore restore;
+    if (n > 0) {
+        std::vector<vrc_caster *> group{h};
+        group.insert(group.end(), h->peers.begin(), h->peers.end());
+        std::vector<std::unique_ptr<EditStage>> stages;
+        // every rank stages its edit (a rank that shares an earlier rank's tree has nothing to do), then all of them commit
+        for (size_t r = 0; r < group.size(); r++) {
+            vrc_caster *g = group[r];
+            stages.emplace_back(new EditStage());
+            bool shared = false;
+            for (size_t k = 0; k < r && svo; k++) shared = shared || group[k]->tree.get() == g->tree.get();
+            if (shared) continue;
+            HIP_TRY(h, hipSetDevice(g->device));
+            const int32_t *d_pos = positions, *d_mat = materials;
+            if (!on_device || g->device != h->device) {               // staged: the host's arrays, or rank 0's for a rank on another GPU
+                VRC_TRY(grow(g, g->edit_in_capacity, n, {{g->d_edit_in, sizeof(int32_t) * 4 * (size_t)n}}));
+                HIP_TRY(h, hipMemcpyAsync(g->d_edit_in, positions, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDefault, g->stream));
+                HIP_TRY(h, hipMemcpyAsync(g->d_edit_in + 3 * n, materials, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, g->stream));
+                d_pos = g->d_edit_in; d_mat = g->d_edit_in + 3 * n;
+            } else {
+                VRC_TRY(wait_for_null_stream(g));
+            }
+            const int rc = edit_stage(g, d_pos, d_mat, n, *stages.back());
+            if (rc != VRC_OK) return g == h ? rc : fail(h, rc, "rank %zu: %s", r, g->error.c_str());
+        }
+        const EditStage &s0 = *stages[0];
+        out.skipped = s0.skipped; out.voxels_changed = s0.changed; out.seconds = s0.seconds;
+        if (svo && s0.commit) {
+            for (auto &st : stages)
+                if (st->ran && st->commit) edit_commit(*st);
+            for (vrc_caster *g : group) VRC_TRY(set_setting(g, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)s0.root));
+            out.bricks_touched = s0.bricks; out.descriptors_added = s0.added;
+        }
+        HIP_TRY(h, hipSetDevice(h->device));
+    }
+    if (svo) {
+        out.n_descriptors = h->tree->n_desc;
+        out.root_index = (uint64_t)setting_or(h, "octree_root_index", 0);
+    }
+    if (info) {
+        const uint32_t bytes = std::min<uint32_t>(info->struct_size, (uint32_t)sizeof(out));
+        out.struct_size = bytes;
+        memcpy(info, &out, bytes);
+    }
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_set_voxels(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    VRC_TRY(edit_check(h, positions, materials, n, flags, "set_voxels"));
+    for (int64_t i = 0; i < n; i++)
+        if (materials[i] < -128 || materials[i] > 127)
+            return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels: materials[%lld] = %d is outside [-128, 127]", (long long)i, (int)materials[i]);
+    return edit_run(h, positions, materials, n, false, info, "set_voxels");
+}
+
+int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    VRC_TRY(edit_check(h, d_positions, d_materials, n, flags, "set_voxels_device"));
+    if (n > 0) {
+        if (((uintptr_t)d_positions & 3u) || ((uintptr_t)d_materials & 3u))
+            return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels_device: positions and materials must be 4-byte aligned");
+        DeviceRestore restore;
+        HIP_TRY(h, hipSetDevice(h->device));
+        if (!query_pointer_ok(h, d_positions) || !query_pointer_ok(h, d_materials))
+            return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels_device: positions and materials must be memory the GPU of the handle (device %d) can read", h->device);
+    }
+    return edit_run(h, static_cast<const int32_t *>(d_positions), static_cast<const int32_t *>(d_materials), n, true, info, "set_voxels_device");
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Everything the host layer (vrc_api.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
 // vrc_api.cpp and by every file that defines one of these functions, so the compiler holds each definition against its
-// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h and voxel_read.h.
+// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h and voxel_edit.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +19,8 @@ struct QueryParams;
 struct BoxParams;
 struct SweepParams;
 struct ReadParams;
+struct EditParams;
+struct EditLevel;
 
 // raycast_kernel.hip
 hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
@@ -66,6 +68,16 @@ hipError_t launch_sweep(const SweepParams &p, hipStream_t stream);
 // voxel_read.hip
 hipError_t launch_voxel_points(const ReadParams &q, hipStream_t stream);
 hipError_t launch_voxel_regions(const ReadParams &q, hipStream_t stream);
+
+// voxel_edit.hip
+hipError_t launch_edit_keys(const EditParams &q, hipStream_t stream);
+hipError_t edit_sort(void *temp, size_t *temp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *order_in, uint32_t *order_out,
+                     int64_t n, int bits, hipStream_t stream);
+hipError_t edit_runs(void *temp, size_t *temp_bytes, const uint64_t *sorted_keys, int64_t n, uint64_t *unique, uint32_t *counts,
+                     unsigned long long *n_runs, hipStream_t stream);
+hipError_t launch_edit_array(const EditParams &q, hipStream_t stream);
+hipError_t launch_edit_bricks(const EditParams &q, hipStream_t stream);
+hipError_t launch_edit_level(const EditParams &q, const EditLevel &level, hipStream_t stream);
 
 // svo_builder_gpu.hip
 int build_shell_terrain_device(hipStream_t stream, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
