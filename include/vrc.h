@@ -521,9 +521,9 @@ int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const in
  *   - Placement is a function of (array before the call, batch) alone: two handles with equal arrays that receive the same batch
  *     end with bit-identical arrays.
  *   - Growth: descriptors_added <= 72 * bricks_touched + 16 * (touched nodes above the bricks) + 1; words of the appended range
- *     that hold nothing are zero.  Old words are never overwritten, so every edit leaves garbage behind and the array only
- *     grows; there is no compaction.  The remedy is a rebuild: vrc_read_regions + vrc_build_dense_grid where the scene fits
- *     that route, building the scene again otherwise.
+ *     that hold nothing are zero.  Old words are never overwritten, so every edit leaves garbage behind and the array grows
+ *     with every batch; vrc_compact_octree (below) drops the garbage and puts the tree back into a dense layout, at any depth
+ *     and for trees that live only in HBM.
  *   - A batch that changes no voxel (voxels_changed == 0) appends nothing and leaves the root where it was.
  *   - Materials: every rebuilt bottom-level descriptor gets an attachment slot of its own.  A tree without attachments stays
  *     without them while every written material is 0 or 5 (trees that live only in HBM must not suddenly need 4 bytes per
@@ -562,6 +562,58 @@ typedef struct vrc_edit_info {          /* size-versioned like vrc_memory2 */
 } vrc_edit_info;
 int vrc_set_voxels(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info);
 int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+
+/* ---- octree compaction ---------------------------------------------------- */
+
+/* Copy the part of the descriptor array that the root reaches into a new, dense, canonically ordered array on the device, remap
+ * the materials, and install the result as an edit's commit does: what vrc_set_voxels leaves behind -- the orphaned paths, the
+ * 72-word brick stride, the far pointers into the old array -- is gone, n_descriptors shrinks to the live tree and the root moves
+ * to index 0.  The scene does not change: reads, queries, frames, hit records and canonical counters are those of before.
+ *
+ * The new array.  n = log2(dim); a descriptor at level l (root: 0) is BOTTOM-LEVEL when l = n - 1 and HOLDS A POINTER when
+ * l < n - 1 and its valid mask is non-zero.  reach = setting compact_near_reach (default 0x7fff, range [16, 0x7fff]).  For a
+ * descriptor D that holds a pointer, with kept children c_0 .. c_{m-1} in slot order: P(c_k) = 1 when c_k's slot is no leaf slot
+ * and c_k holds a pointer; the subtree words S(c) are 0 when P(c) = 0; c_k is FAR when P(c_k) and 16 + sum_{j<k} S(c_j) > reach;
+ * f = the number of far children; S(D) = m + f + sum_k S(c_k).  Placement is pre-order: the root at index 0, its child block at
+ * 1; a child block at B holds the children at B .. B+m-1, the far slots of the far children (in child order) at B+m .. B+m+f-1,
+ * then the children's own blocks in child order, c_k's at T_k = B + m + f + sum_{j<k} S(c_j).  A near pointer is T_k - (B+k); a
+ * far pointer is 0x8000 | (slot - (B+k)) and the slot holds T_k.  (The far rule is pessimistic on purpose: the constant 16 --
+ * eight words and eight far slots -- makes it computable bottom-up.)  Every copied word keeps bits 16-63 of the old word; bits
+ * 0-15 are the new pointer, zero where no walker follows one (bottom-level descriptors, valid mask 0, the words of leaf slots).
+ * n_descriptors = 1 + S(root), and every word is the root, a word of a reachable child block or a far slot one descriptor names.
+ * The layout is a function of the tree alone: two arrays that encode the same tree (with the same words in their leaf slots)
+ * compact to identical arrays, and compacting twice in a row leaves the array bit-identical.
+ *
+ * Materials.  A tree without attachments stays without.  Otherwise the attachment slots named by the lookup of a reachable
+ * bottom-level descriptor are kept, in increasing old-slot order, and the rest are dropped; descriptors that shared a slot still
+ * share it; lookup[new] is the remapped slot for a bottom-level descriptor and 0 for every other word.  (When no descriptor names
+ * a slot, one slot of eight 5s stays: a tree with materials never has an empty attachment array.)
+ *
+ * Host.  Out of place: the new arrays are allocated at their size + edit_reserve (the edit's rule) BESIDE the old ones, which are
+ * freed at the commit once the device is idle; a tree that does not fit twice is VRC_ERR_OUT_OF_MEMORY (in-place compaction does
+ * not exist).  Atomic: on any failure nothing has changed.  The commit moves n_descriptors, octree_root_index (to 0),
+ * n_attachments and the capacities, and drops the coarse table and the empty boxes as an edit does.  A group handle replicates
+ * the call: ranks that share rank 0's tree take the new root, ranks with their own copy run the same compaction (the layout is
+ * canonical, so the copies stay equal); a tree also held OUTSIDE the group is VRC_ERR_LIMIT, as for edits.  Otherwise the host
+ * rules of vrc_set_voxels: synchronous on the handle's stream; image, records, counters, timing and vrc_last_kernel untouched;
+ * the caller's device restored.  The call's scratch (about 42 bytes per pointer-holding descriptor, a fifth of a tree) is freed
+ * before it returns.  using_octree != 0 (the array branch) succeeds and changes nothing.
+ * flags: VRC_COMPACT_DRY_RUN measures only (the sizes, the far children, the used attachment slots), fills info and changes
+ * nothing -- for a host that compacts when descriptors_before is a multiple of n_descriptors.  Any other bit, a null handle, an
+ * info whose struct_size is below 4 or compact_near_reach outside its range: VRC_ERR_INVALID_ARGUMENT; VRC_ERR_NOT_READY as for
+ * ray queries; an array whose pointers leave it or that is no tree: VRC_ERR_INVALID_ARGUMENT.                                 */
+#define VRC_COMPACT_DRY_RUN 1u
+typedef struct vrc_compact_info {       /* size-versioned like vrc_edit_info */
+    uint32_t struct_size;               /* in: sizeof the caller's struct; out: bytes written */
+    uint32_t reserved_;
+    uint64_t descriptors_before;        /* n_descriptors before the call */
+    uint64_t n_descriptors, root_index; /* the tree after the call (a dry run: as it would be) */
+    uint64_t live_descriptors;          /* reachable words without far slots */
+    uint64_t far_slots;
+    uint64_t attachments_before, n_attachments;
+    double   seconds;                   /* device time of the call's kernels */
+} vrc_compact_info;
+int vrc_compact_octree(vrc_caster *h, uint32_t flags, vrc_compact_info *info);
 
 /* Device pointers of the resident frame buffers (float4[w*h], int32[8*w*h]);
  * lets a host that owns the GPU (e.g. a torch process) consume the frame

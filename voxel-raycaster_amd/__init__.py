@@ -99,6 +99,15 @@ class EditInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved_")}
 
 
+class CompactInfo(C.Structure):
+    _fields_ = ([("struct_size", C.c_uint32), ("reserved_", C.c_uint32)]
+                + [(n, C.c_uint64) for n in ("descriptors_before", "n_descriptors", "root_index", "live_descriptors", "far_slots",
+                                             "attachments_before", "n_attachments")] + [("seconds", C.c_double)])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved_")}
+
+
 class IndexAuditEntry(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in ("accesses", "max_index", "extent", "violations")] + [("first_index", C.c_int64), ("first_extent", C.c_uint64)]
                 + [(n, C.c_uint32) for n in ("first_block", "first_site", "extent_published", "reserved_")])
@@ -204,9 +213,11 @@ SIGNATURES = {
     "vrc_read_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),
     "vrc_set_voxels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_set_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_compact_octree": (C.c_int, [_H, C.c_uint32, C.POINTER(CompactInfo)]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
+COMPACT_DRY_RUN = 1
 KERNEL_NONE, KERNEL_SVO, KERNEL_JUMP, KERNEL_ARRAY = 0, 1, 2, 3      # vrc_last_kernel: family
 # ray queries (vrc_cast_rays): the flag, and the bits of record field 5
 RAY_AS_PIXEL = 1
@@ -938,6 +949,18 @@ class CLCaster:
         info = EditInfo()
         info.struct_size = C.sizeof(EditInfo)
         if not self._ok(lib.vrc_set_voxels_device(self._h, C.c_void_p(positions_ptr), C.c_void_p(materials_ptr), int(n), 0, C.byref(info))):
+            raise VrcError(self.last_error())
+        return info.as_dict()
+
+    # -- octree compaction (vrc_compact_octree, include/vrc.h)
+    def compact_octree(self, dry_run: bool = False) -> dict:
+        """Copy what the root of the resident octree reaches into a new dense, canonically ordered array and install it (the
+        garbage the edits left is dropped, the root moves to 0); dry_run only measures.  Returns vrc_compact_info as a dict:
+        descriptors_before, n_descriptors, root_index, live_descriptors, far_slots, attachments_before, n_attachments, seconds.
+        Raises on failure."""
+        info = CompactInfo()
+        info.struct_size = C.sizeof(CompactInfo)
+        if not self._ok(lib.vrc_compact_octree(self._h, COMPACT_DRY_RUN if dry_run else 0, C.byref(info))):
             raise VrcError(self.last_error())
         return info.as_dict()
 

@@ -182,6 +182,12 @@ public:
         return ok(vrc_set_voxels_device(h_, d_positions, d_materials, n, 0u, info));
     }
 
+    // extension: drop the garbage the edits leave in the resident octree (vrc_compact_octree); dry_run measures only
+    bool compact_octree(bool dry_run = false, vrc_compact_info *info = nullptr) {
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_compact_octree(h_, dry_run ? VRC_COMPACT_DRY_RUN : 0u, info));
+    }
+
     int last_status() const { return status_; }
     std::string last_error() const { return h_ ? vrc_last_error(h_) : "not initialised"; }
     vrc_caster *handle() { return h_; }

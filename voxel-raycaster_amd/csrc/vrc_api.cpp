@@ -26,6 +26,7 @@
 #include "../../include/vrc.h"
 #include "box_query.h"
 #include "box_sweep.h"
+#include "octree_compact.h"
 #include "raycast_query.h"
 #include "voxel_edit.h"
 #include "voxel_read.h"
@@ -36,7 +37,7 @@
 #include "index_audit.hpp"
 namespace vrc {
 #define VRC_AUDIT_DECLARE(name) hipError_t audit_publish_##name(const unsigned long long *extent_plus_1); hipError_t audit_collect_##name(audit::Stat *out, unsigned long long *extent_plus_1, int clear);
-VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit)
+VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit) VRC_AUDIT_DECLARE(compact)
 #undef VRC_AUDIT_DECLARE
 }  // namespace vrc
 #endif
@@ -313,6 +314,7 @@ const AuditTu kAuditTus[] = {
     {vrc::audit_publish_boxes, vrc::audit_collect_boxes},     {vrc::audit_publish_query, vrc::audit_collect_query},
     {vrc::audit_publish_boxq, vrc::audit_collect_boxq},       {vrc::audit_publish_sweep, vrc::audit_collect_sweep},
     {vrc::audit_publish_read, vrc::audit_collect_read},       {vrc::audit_publish_edit, vrc::audit_collect_edit},
+    {vrc::audit_publish_compact, vrc::audit_collect_compact},
 };
 hipError_t audit_publish(const AuditExtents &x) {
     hipError_t e = hipDeviceSynchronize();
@@ -2325,15 +2327,8 @@ int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const in
 // ---------------------------------------------------------------------------------------------------------------------------
 namespace {
 
-// the argument checks of both calls, then the readiness checks of the ray queries; nothing is launched when one fails
-int edit_check(vrc_caster *h, const void *positions, const void *materials, int64_t n, uint32_t flags, const char *what) {
-    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
-    if (flags) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)flags);
-    if (n > 0 && (!positions || !materials)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null positions or materials", what);
-    if (n > INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 edits in one batch", what);
-    VRC_TRY(query_check(h, positions, n, 0, 0, materials, what));
-    if (setting_or(h, "using_octree", 0) != 0) return VRC_OK;
-    // a holder of the tree outside this group would keep rendering from the old root: its setting cannot be moved from here
+// a holder of the tree outside this group would keep rendering from the old root: its setting cannot be moved from here
+int group_alone_holds_trees(vrc_caster *h, const char *what) {
     std::vector<const vrc_caster *> group{h};
     group.insert(group.end(), h->peers.begin(), h->peers.end());
     for (const vrc_caster *g : group) {
@@ -2344,6 +2339,17 @@ int edit_check(vrc_caster *h, const void *positions, const void *materials, int6
             return fail(h, VRC_ERR_LIMIT, "%s: the tree is also held by a handle outside this group (vrc_assign_octree_from); its root cannot be moved from here", what);
     }
     return VRC_OK;
+}
+
+// the argument checks of both calls, then the readiness checks of the ray queries; nothing is launched when one fails
+int edit_check(vrc_caster *h, const void *positions, const void *materials, int64_t n, uint32_t flags, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    if (flags) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)flags);
+    if (n > 0 && (!positions || !materials)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null positions or materials", what);
+    if (n > INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 edits in one batch", what);
+    VRC_TRY(query_check(h, positions, n, 0, 0, materials, what));
+    if (setting_or(h, "using_octree", 0) != 0) return VRC_OK;
+    return group_alone_holds_trees(h, what);
 }
 
 // What one handle's edit has prepared and edit_commit installs.  Until then the tree is what it was: the appended words lie
@@ -2637,6 +2643,251 @@ int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_
             return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels_device: positions and materials must be memory the GPU of the handle (device %d) can read", h->device);
     }
     return edit_run(h, static_cast<const int32_t *>(d_positions), static_cast<const int32_t *>(d_materials), n, true, info, "set_voxels_device");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// octree compaction (vrc_compact_octree, octree_compact.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// device memory of one call: the lists, scans and sizes of every level.  Freed when the call ends, so none of it outlives the tree.
+struct CompactScratch {
+    int device = 0;
+    std::vector<void *> held;
+    explicit CompactScratch(int dev) : device(dev) {}
+    CompactScratch(const CompactScratch &) = delete;
+    CompactScratch &operator=(const CompactScratch &) = delete;
+    template <class T>
+    hipError_t get(T *&p, uint64_t n) {
+        void *v = nullptr;
+        const hipError_t e = hipMalloc(&v, (size_t)std::max<uint64_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) { held.push_back(v); p = static_cast<T *>(v); }
+        return e;
+    }
+    ~CompactScratch() {
+        DeviceRestore restore;
+        (void)hipSetDevice(device);
+        for (void *v : held) (void)hipFree(v);
+        (void)hipGetLastError();
+    }
+};
+
+// What one handle's compaction has prepared: the staged arrays edit_commit installs, and the counts of vrc_compact_info.
+struct CompactStage : EditStage {
+    uint64_t before = 0, far = 0, attach_before = 0;
+};
+
+// One handle's compaction up to the commit (current device: g->device).  dry: sweeps 1 and 2 and the used attachment slots only.
+int compact_stage(vrc_caster *g, bool dry, CompactStage &st) {
+    st.h = g; st.ran = true;
+    vrc_tree *t = g->tree.get();
+    std::unique_lock<std::mutex> lock(t->guard);
+    HIP_TRY(g, hipStreamSynchronize(g->stream));                      // a frame in flight finishes first
+    vrc::CompactParams q;
+    memset(&q, 0, sizeof(q));
+    bind_scene(g, t, q.scene);
+    q.scene.coarse = nullptr; q.scene.coarse_log2 = 0;
+    const int n = q.scene.log2_dim;
+    const bool have = q.scene.attach_lookup != nullptr;
+    q.n_old = t->n_desc;
+    q.n_attach_old = have ? std::max<uint64_t>(t->n_attach, 1) : 0;
+    q.reach = (uint64_t)setting_or(g, "compact_near_reach", vrc::kCompactReachMax);
+    st.before = q.n_old; st.attach_before = q.n_attach_old;
+    CompactScratch mem(g->device);
+    EditTimer timer;
+    HIP_TRY(g, timer.init());
+    // the kernels run in segments, each ended by the read-back that sizes the next one
+    auto begin = [&]() { return hipEventRecord(timer.a, g->stream); };
+    auto end = [&]() {
+        hipError_t e = hipEventRecord(timer.b, g->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+        if (e == hipSuccess) timer.add(&st.seconds);
+        return e;
+    };
+    auto scan = [&](const uint64_t *in, uint64_t *out, uint64_t count) {
+        size_t bytes = 0;
+        char *temp = nullptr;
+        hipError_t e = vrc::compact_scan(nullptr, &bytes, in, out, count, g->stream);
+        if (e == hipSuccess) e = mem.get(temp, bytes);
+        if (e == hipSuccess) e = vrc::compact_scan(temp, &bytes, in, out, count, g->stream);
+        return e;
+    };
+    HIP_TRY(g, mem.get(q.counters, vrc::kCompactCounters));
+    HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(unsigned long long) * vrc::kCompactCounters, g->stream));
+
+    // sweep 1, top-down: the pointer-holding descriptors of every level above the bottom
+    uint64_t root_word = 0;
+    HIP_TRY(g, hipMemcpy(&root_word, t->d_desc + q.scene.root_index, sizeof(root_word), hipMemcpyDeviceToHost));
+    std::vector<vrc::CompactLevel> levels;
+    uint64_t count = (n > 1 && ((root_word >> 16) & 0xffULL)) ? 1 : 0;
+    uint64_t *list = nullptr;
+    if (count) {
+        HIP_TRY(g, mem.get(list, 1));
+        HIP_TRY(g, hipMemcpy(list, &q.scene.root_index, sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    for (int l = 0; l <= n - 2 && count > 0; l++) {
+        vrc::CompactLevel L;
+        memset(&L, 0, sizeof(L));
+        L.list = list; L.count = (int64_t)count; L.level = l; L.children_bottom = l == n - 2 ? 1 : 0;
+        uint64_t *sums = nullptr, *base = nullptr;
+        HIP_TRY(g, mem.get(L.pmask, count)); HIP_TRY(g, mem.get(L.farmask, count)); HIP_TRY(g, mem.get(L.size, count));
+        HIP_TRY(g, mem.get(L.cnt, count + 1)); HIP_TRY(g, mem.get(sums, count + 1)); HIP_TRY(g, mem.get(base, count));
+        L.scan = sums; L.base = base;
+        HIP_TRY(g, begin());
+        if (!levels.empty()) HIP_TRY(g, vrc::launch_compact_level(q, levels.back(), 1, g->stream));    // (this level's list)
+        HIP_TRY(g, vrc::launch_compact_level(q, L, 0, g->stream));
+        HIP_TRY(g, scan(L.cnt, sums, count + 1));
+        HIP_TRY(g, end());
+        uint64_t next = 0;
+        HIP_TRY(g, hipMemcpy(&next, sums + count, sizeof(next), hipMemcpyDeviceToHost));
+        if (next > q.n_old) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: level %d holds more descriptors than the array: not a tree", l + 1);
+        list = nullptr;
+        if (next) HIP_TRY(g, mem.get(list, next));
+        L.next_list = list;
+        levels.push_back(L);
+        count = next;
+    }
+    if (count) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: the bottom level holds pointers: not a tree");
+    for (size_t l = 0; l + 1 < levels.size(); l++) { levels[l].size_below = levels[l + 1].size; levels[l].base_below = const_cast<uint64_t *>(levels[l + 1].base); }
+
+    // sweep 2, bottom-up: the subtree sizes and the far children
+    uint64_t below_root = 0;
+    if (!levels.empty()) {
+        HIP_TRY(g, begin());
+        for (size_t l = levels.size(); l-- > 0;) HIP_TRY(g, vrc::launch_compact_level(q, levels[l], 2, g->stream));
+        HIP_TRY(g, end());
+        HIP_TRY(g, hipMemcpy(&below_root, levels[0].size, sizeof(below_root), hipMemcpyDeviceToHost));
+    }
+    unsigned long long c[vrc::kCompactCounters];
+    HIP_TRY(g, hipMemcpy(c, q.counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[vrc::kCompactBad]) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: the tree points outside its array (%llu indices)", c[vrc::kCompactBad]);
+    st.n_desc = 1 + below_root; st.far = c[vrc::kCompactFar]; st.root = 0;
+    if (st.n_desc >= (1ULL << 47)) return fail(g, VRC_ERR_LIMIT, "compact_octree: more than 2^47 descriptors");
+
+    // the new arrays, beside the old ones until the commit
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+    auto staged = [&](auto *&p, uint64_t &cap, uint64_t need, size_t elem) -> int {
+        cap = need + edit_reserve_for(g, need, elem, free_b);
+        const hipError_t e = hipMalloc((void **)&p, cap * elem);
+        if (e == hipSuccess) return VRC_OK;
+        (void)hipGetLastError();
+        p = nullptr;
+        return fail(g, e == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE, "compact_octree: allocating the new arrays (%llu words) beside the old ones failed: %s",
+                    (unsigned long long)need, hipGetErrorString(e));
+    };
+    if (!dry) {
+        VRC_TRY(staged(st.desc, st.cap_desc, st.n_desc, sizeof(uint64_t)));
+        q.out = st.desc; q.n_out = st.n_desc;
+        if (have) {
+            VRC_TRY(staged(st.lookup, st.cap_lookup, st.n_desc, sizeof(uint32_t)));
+            HIP_TRY(g, hipMemsetAsync(st.lookup, 0, st.n_desc * sizeof(uint32_t), g->stream));
+            q.out_lookup = st.lookup;
+        }
+        if (!levels.empty()) {
+            const uint64_t one = 1;
+            HIP_TRY(g, hipMemcpy(const_cast<uint64_t *>(levels[0].base), &one, sizeof(one), hipMemcpyHostToDevice));
+        }
+    }
+    uint64_t *remap = nullptr;
+    if (have) {
+        HIP_TRY(g, mem.get(q.used, q.n_attach_old + 1));
+        HIP_TRY(g, mem.get(remap, q.n_attach_old + 1));
+        HIP_TRY(g, hipMemsetAsync(q.used, 0, (q.n_attach_old + 1) * sizeof(uint64_t), g->stream));
+    }
+
+    // sweep 3, top-down: the blocks, the far slots, the lookup words, the used attachment slots (a dry run: only those, which
+    // the parents of the bottom level raise)
+    HIP_TRY(g, begin());
+    if (!dry || have) HIP_TRY(g, vrc::launch_compact_root(q, g->stream));
+    for (const vrc::CompactLevel &L : levels)
+        if (!dry || (have && L.children_bottom)) HIP_TRY(g, vrc::launch_compact_level(q, L, 3, g->stream));
+    if (have) HIP_TRY(g, scan(q.used, remap, q.n_attach_old + 1));
+    HIP_TRY(g, end());
+    if (have) {
+        uint64_t kept = 0;
+        HIP_TRY(g, hipMemcpy(&kept, remap + q.n_attach_old, sizeof(kept), hipMemcpyDeviceToHost));
+        st.n_attach = std::max<uint64_t>(kept, 1);                   // (a tree with materials keeps a slot: slot 0 = eight 5s, as the edit creates it)
+        if (!dry) {
+            VRC_TRY(staged(st.attach, st.cap_attach, st.n_attach, sizeof(uint64_t)));
+            HIP_TRY(g, begin());
+            if (!kept) HIP_TRY(g, hipMemsetAsync(st.attach, 0x05, sizeof(uint64_t), g->stream));
+            HIP_TRY(g, vrc::launch_compact_materials(q, remap, st.n_desc, st.attach, kept, g->stream));
+            HIP_TRY(g, end());
+        }
+    }
+    HIP_TRY(g, hipMemcpy(c, q.counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[vrc::kCompactBad]) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: the tree points outside its array (%llu indices)", c[vrc::kCompactBad]);
+    st.commit = !dry;
+    return VRC_OK;
+}
+
+int compact_run(vrc_caster *h, bool dry, vrc_compact_info *info) {
+    vrc_compact_info out;
+    memset(&out, 0, sizeof(out));
+    DeviceRestore restore;
+    if (setting_or(h, "using_octree", 0) == 0) {
+        std::vector<vrc_caster *> group{h};
+        group.insert(group.end(), h->peers.begin(), h->peers.end());
+        std::vector<std::unique_ptr<CompactStage>> stages;
+        // every rank stages its new arrays (a rank that shares an earlier rank's tree has nothing to do), then all of them commit
+        for (size_t r = 0; r < group.size(); r++) {
+            vrc_caster *g = group[r];
+            stages.emplace_back(new CompactStage());
+            bool shared = false;
+            for (size_t k = 0; k < r; k++) shared = shared || group[k]->tree.get() == g->tree.get();
+            if (shared) continue;
+            HIP_TRY(h, hipSetDevice(g->device));
+            const int rc = compact_stage(g, dry, *stages.back());
+            if (rc != VRC_OK) return g == h ? rc : fail(h, rc, "rank %zu: %s", r, g->error.c_str());
+        }
+        const CompactStage &s0 = *stages[0];
+        if (!dry) {
+            for (auto &st : stages)
+                if (st->ran && st->commit) edit_commit(*st);
+            for (vrc_caster *g : group) VRC_TRY(set_setting(g, "octree_root_index", "OCTREE_ROOT_INDEX", 0));
+#ifdef VRC_INDEX_AUDIT
+            // the tables still hold the old tree's extents, and the new arrays are SHORTER: what runs next is held against the new ones
+            for (vrc_caster *g : group) {
+                HIP_TRY(h, hipSetDevice(g->device));
+                std::lock_guard<std::mutex> lock(g->tree->guard);
+                AuditExtents x;
+                audit_tree(x, g->tree.get());
+                VRC_AUDIT_PUBLISH(h, x);
+            }
+#endif
+        }
+        HIP_TRY(h, hipSetDevice(h->device));
+        out.descriptors_before = s0.before; out.n_descriptors = s0.n_desc; out.root_index = 0;
+        out.live_descriptors = s0.n_desc - s0.far; out.far_slots = s0.far;
+        out.attachments_before = s0.attach_before; out.n_attachments = s0.n_attach;
+        out.seconds = s0.seconds;
+    }
+    if (info) {
+        const uint32_t bytes = std::min<uint32_t>(info->struct_size, (uint32_t)sizeof(out));
+        out.struct_size = bytes;
+        memcpy(info, &out, bytes);
+    }
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_compact_octree(vrc_caster *h, uint32_t flags, vrc_compact_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    const char *what = "compact_octree";
+    if (flags & ~(uint32_t)VRC_COMPACT_DRY_RUN) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_COMPACT_DRY_RUN));
+    if (info && info->struct_size < sizeof(uint32_t)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: info->struct_size is not set", what);
+    const int64_t reach = setting_or(h, "compact_near_reach", vrc::kCompactReachMax);
+    if (reach < vrc::kCompactReachMin || reach > vrc::kCompactReachMax)
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: compact_near_reach = %lld is outside [%lld, %lld]", what, (long long)reach, (long long)vrc::kCompactReachMin, (long long)vrc::kCompactReachMax);
+    VRC_TRY(query_check(h, nullptr, 0, 0, 0, nullptr, what));
+    if (setting_or(h, "using_octree", 0) == 0) VRC_TRY(group_alone_holds_trees(h, what));
+    return compact_run(h, (flags & VRC_COMPACT_DRY_RUN) != 0, info);
 }
 
 }  // extern "C"

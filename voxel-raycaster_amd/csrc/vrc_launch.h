@@ -1,6 +1,6 @@
 // Everything the host layer (vrc_api.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
 // vrc_api.cpp and by every file that defines one of these functions, so the compiler holds each definition against its
-// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h and voxel_edit.h.
+// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h, voxel_edit.h and octree_compact.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,8 @@ struct SweepParams;
 struct ReadParams;
 struct EditParams;
 struct EditLevel;
+struct CompactParams;
+struct CompactLevel;
 
 // raycast_kernel.hip
 hipError_t launch_fill_image(float *image, size_t n_pixels, hipStream_t stream);
@@ -78,6 +80,12 @@ hipError_t edit_runs(void *temp, size_t *temp_bytes, const uint64_t *sorted_keys
 hipError_t launch_edit_array(const EditParams &q, hipStream_t stream);
 hipError_t launch_edit_bricks(const EditParams &q, hipStream_t stream);
 hipError_t launch_edit_level(const EditParams &q, const EditLevel &level, hipStream_t stream);
+
+// octree_compact.hip
+hipError_t launch_compact_level(const CompactParams &q, const CompactLevel &level, int pass, hipStream_t stream);
+hipError_t launch_compact_root(const CompactParams &q, hipStream_t stream);
+hipError_t launch_compact_materials(const CompactParams &q, const uint64_t *remap, uint64_t n_new, uint64_t *attach, uint64_t n_attach_new, hipStream_t stream);
+hipError_t compact_scan(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t stream);
 
 // svo_builder_gpu.hip
 int build_shell_terrain_device(hipStream_t stream, uint32_t depth, uint64_t seed, int32_t thickness, int32_t octave_floor,
