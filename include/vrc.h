@@ -563,6 +563,68 @@ typedef struct vrc_edit_info {          /* size-versioned like vrc_memory2 */
 int vrc_set_voxels(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info);
 int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info);
 
+/* ---- region edits --------------------------------------------------------- */
+
+/* Change whole regions of the scene: fill axis-aligned boxes with a material (dig a crater, carve a corridor, paint a wall) and
+ * paste dense int8 blocks (stamp a prefab) -- the inverse of vrc_read_regions -- without expanding the shape into one
+ * (x, y, z, material) tuple per voxel.  An operation is six integers; no voxel of it is enumerated on the host or on the device.
+ *
+ * Operations
+ *   vrc_fill_boxes      boxes int32[6 n]: lo x, y, z, then size x, y, z, every size >= 1; box i covers [lo, lo + size).
+ *                       materials int32[n], each in [-128, 127]; 0 clears.
+ *   vrc_write_regions   exactly the arguments and the block layout of vrc_read_regions: n regions of one common size
+ *                       (sx, sy, sz), lo int32[3 n], region i owns bytes [i V, (i + 1) V) of data, V = sx sy sz, and byte
+ *                       (x - lo.x) + sx * ((y - lo.y) + sy * (z - lo.z)) of region i is the material for (x, y, z).
+ *                       n_bytes is the size of data and must be at least n V.
+ *   lo may be any int32; lo + size is formed in 64 bits: a box at lo = INT32_MIN with size INT32_MAX is legal.  The part of an
+ *   operation outside the scene -- [0, dim)^3 for the tree; map_dim, or an index past the array, for the map -- is ignored
+ *   without comment.  An operation that touches no voxel of the scene is counted in info->skipped.  In the _device fill variant
+ *   an operation with a material outside [-128, 127] or a size < 1 cannot be refused without a read-back: it is skipped and
+ *   counted; the host call refuses it with VRC_ERR_INVALID_ARGUMENT.
+ *
+ * Order.  The result is what applying the operations IN INDEX ORDER gives: operation i sees the scene as operations 0 .. i-1
+ * left it.  That decides overlaps, and it decides the flags, which test the material a voxel has at that moment:               */
+#define VRC_WRITE_WHERE_EMPTY 1u   /* write only voxels whose material is 0 at that moment (build, never overwrite) */
+#define VRC_WRITE_WHERE_SOLID 2u   /* write only voxels whose material is non-zero at that moment (paint, dig) */
+#define VRC_WRITE_SKIP_ZERO   4u   /* vrc_write_regions only: a 0 byte of the block leaves the voxel alone (stamp a prefab) */
+/* WHERE_EMPTY | WHERE_SOLID together is VRC_ERR_INVALID_ARGUMENT; so is SKIP_ZERO on a fill, and so is any other bit.
+ *
+ * Everything else is vrc_set_voxels' contract.  The branch follows using_octree.  The SVO edit is the same append-only,
+ * path-copying edit with the same commit: the edited tree is the tree vrc_build_dense_grid(..., VRC_BUILD_ATTACHMENTS) builds
+ * from the edited grid, up to layout, empty subtrees pruned up to the root, solid regions never collapsed into leaves; the same
+ * growth bound (descriptors_added <= 72 * bricks_touched + 16 * touched nodes above the bricks + 1), the same edit_reserve,
+ * the same atomicity on every failure, the coarse table and the empty boxes dropped the same way; a group replicates the call
+ * the same way and a tree held outside the group is VRC_ERR_LIMIT.  The host rules and vrc_edit_info are the same, where
+ * `skipped` counts operations and `bricks_touched` counts every brick that the in-scene part of an operation overlaps, whether
+ * or not the brick changed (array branch: 0).  A batch that changes no voxel appends nothing, leaves the root where it was and
+ * reports bricks_touched = descriptors_added = 0, as vrc_set_voxels does.
+ *
+ * Placement is a function of (array before the call, set of touched bricks, resulting voxels) alone: the touched bricks sit in
+ * Morton-key order at brick_base + 72 u and the ancestors are appended exactly as vrc_set_voxels appends them.  So with
+ * flags = 0 a fill produces an array, a lookup and attachments bit-identical to those vrc_set_voxels produces for the same
+ * boxes expanded to their in-scene positions in operation order, and so does a paste.
+ *
+ * Materials.  A tree without attachments stays without them when every fill operation that touches the scene has material 0
+ * or 5 and every byte of the in-scene part of every pasted region is 0 or 5 -- whatever the flags are, so the decision is a
+ * function of the batch and the scene size alone.  Otherwise the lookup and slot 0 are created as vrc_set_voxels creates them.
+ *
+ * Array branch.  Fills and pastes go into the map at the frame's index x + dx * (y + dz * z).  A map with dy > dz, where that
+ * index is not one-to-one over map_dim, is refused with VRC_ERR_LIMIT and nothing is changed.
+ *
+ * Limits.  VRC_ERR_LIMIT when n > 2^31 - 1, when the batch has more than 2^31 - 1 (brick, operation) pairs -- a pair is one
+ * map-aligned 8^3 brick overlapped by one operation -- or when n V overflows size_t (or exceeds 2^63), as in vrc_read_regions.
+ * VRC_ERR_OUT_OF_MEMORY, with nothing changed, when the appended range does not fit: a fill of a whole deep map is such a case.
+ * The _device variants take memory the handle's GPU can read and wait for the null stream first; boxes, materials and lo must
+ * be 4-byte aligned, the blocks may have any alignment.
+ * Errors, with nothing launched and nothing changed: VRC_ERR_INVALID_ARGUMENT for a null handle or pointer, n < 0, the flag
+ * combinations above, a size component < 1 (host fill and both pastes), n_bytes < n V, a misaligned device pointer, an info
+ * whose struct_size is below 4 or (host fill) a material outside [-128, 127]; VRC_ERR_NOT_READY as for ray queries.  n = 0
+ * succeeds and changes nothing.                                                                                              */
+int vrc_fill_boxes(vrc_caster *h, const int32_t *boxes, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+int vrc_fill_boxes_device(vrc_caster *h, const void *d_boxes, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+int vrc_write_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], const int8_t *data, size_t n_bytes, uint32_t flags, vrc_edit_info *info);
+int vrc_write_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], const void *d_data, size_t n_bytes, uint32_t flags, vrc_edit_info *info);
+
 /* ---- octree compaction ---------------------------------------------------- */
 
 /* Copy the part of the descriptor array that the root reaches into a new, dense, canonically ordered array on the device, remap

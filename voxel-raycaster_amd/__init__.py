@@ -213,11 +213,17 @@ SIGNATURES = {
     "vrc_read_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),
     "vrc_set_voxels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_set_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_fill_boxes": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_fill_boxes_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_write_regions": (C.c_int, [_H, _i32p, C.c_int64, _i32p, C.POINTER(C.c_int8), C.c_size_t, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_write_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_compact_octree": (C.c_int, [_H, C.c_uint32, C.POINTER(CompactInfo)]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
 BUILD_ATTACHMENTS = 2
 COMPACT_DRY_RUN = 1
+# region edits (vrc_fill_boxes / vrc_write_regions): the flags
+WRITE_WHERE_EMPTY, WRITE_WHERE_SOLID, WRITE_SKIP_ZERO = 1, 2, 4
 KERNEL_NONE, KERNEL_SVO, KERNEL_JUMP, KERNEL_ARRAY = 0, 1, 2, 3      # vrc_last_kernel: family
 # ray queries (vrc_cast_rays): the flag, and the bits of record field 5
 RAY_AS_PIXEL = 1
@@ -951,6 +957,73 @@ class CLCaster:
         if not self._ok(lib.vrc_set_voxels_device(self._h, C.c_void_p(positions_ptr), C.c_void_p(materials_ptr), int(n), 0, C.byref(info))):
             raise VrcError(self.last_error())
         return info.as_dict()
+
+    # -- region edits (vrc_fill_boxes / vrc_write_regions, include/vrc.h)
+    @staticmethod
+    def _write_flags(what, where, skip_zero=False) -> int:
+        if where not in (None, "empty", "solid"):
+            raise VrcError(f"{what}: where must be None, 'empty' or 'solid', got {where!r}")
+        return ((WRITE_WHERE_EMPTY if where == "empty" else WRITE_WHERE_SOLID if where == "solid" else 0)
+                | (WRITE_SKIP_ZERO if skip_zero else 0))
+
+    def _edit_call(self, fn, *args) -> dict:
+        info = EditInfo()
+        info.struct_size = C.sizeof(EditInfo)
+        if not self._ok(fn(self._h, *args, C.byref(info))):
+            raise VrcError(self.last_error())
+        return info.as_dict()
+
+    def fill_boxes(self, lo: np.ndarray, size, materials, where: Optional[str] = None) -> dict:
+        """Fill the boxes [lo[i], lo[i] + size[i]) with materials[i], in index order: lo (n, 3) int32, size one triple or (n, 3),
+        every component >= 1, materials (n,) or one value; 0 clears, the part outside the scene is ignored.  where = "empty"
+        writes only voxels that are empty at that moment, "solid" only those that are not.  Returns vrc_edit_info as a dict
+        (skipped counts boxes that touch no voxel of the scene).  Raises on failure."""
+        c = np.ascontiguousarray(lo, dtype=np.int32)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise VrcError(f"fill_boxes: lo must have shape (n, 3), got {c.shape}")
+        sz = np.asarray(size)
+        if sz.shape not in ((3,), c.shape):
+            raise VrcError(f"fill_boxes: size must have shape (3,) or {c.shape}, got {sz.shape}")
+        m = np.asarray(materials)
+        if m.shape not in ((), (c.shape[0],)):
+            raise VrcError(f"fill_boxes: materials must be one value or have shape ({c.shape[0]},), got {m.shape}")
+        for name, v in (("size", sz), ("material", m)):
+            if v.size and (v.min() < -2 ** 31 or v.max() >= 2 ** 31):
+                raise VrcError(f"fill_boxes: a {name} does not fit int32")
+        boxes = np.empty((c.shape[0], 6), dtype=np.int32)
+        boxes[:, :3], boxes[:, 3:] = c, sz
+        m = np.ascontiguousarray(np.broadcast_to(m, (c.shape[0],)), dtype=np.int32)
+        return self._edit_call(lib.vrc_fill_boxes, _ptr(boxes, _i32p), _ptr(m, _i32p), c.shape[0], self._write_flags("fill_boxes", where))
+
+    def fill_boxes_device(self, boxes_ptr: int, materials_ptr: int, n: int, where: Optional[str] = None) -> dict:
+        """fill_boxes on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 6 int32 = lo, size and n int32);
+        a box with a size < 1 or a material outside [-128, 127] is skipped and counted."""
+        return self._edit_call(lib.vrc_fill_boxes_device, C.c_void_p(boxes_ptr), C.c_void_p(materials_ptr), int(n),
+                               self._write_flags("fill_boxes_device", where))
+
+    def write_regions(self, lo: np.ndarray, data: np.ndarray, skip_zero: bool = False, where: Optional[str] = None) -> dict:
+        """Paste dense blocks, the inverse of read_regions: lo (n, 3) int32, data (n, sz, sy, sx) int8 -- the shape read_regions
+        returns -- so data[i, z - lo_z, y - lo_y, x - lo_x] becomes the material of (x, y, z), in index order.  skip_zero: a 0
+        byte leaves the voxel alone; where as in fill_boxes.  Returns vrc_edit_info as a dict.  Raises on failure."""
+        c = np.ascontiguousarray(lo, dtype=np.int32)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise VrcError(f"write_regions: lo must have shape (n, 3), got {c.shape}")
+        d = np.asarray(data)
+        if d.dtype != np.int8 or d.ndim != 4 or d.shape[0] != c.shape[0] or min(d.shape[1:]) < 1:
+            raise VrcError(f"write_regions: data must be int8 of shape ({c.shape[0]}, sz, sy, sx), got {d.dtype} {d.shape}")
+        d = np.ascontiguousarray(d)
+        sz = np.array([d.shape[3], d.shape[2], d.shape[1]], dtype=np.int32)
+        return self._edit_call(lib.vrc_write_regions, _ptr(c, _i32p), c.shape[0], _ptr(sz, _i32p), _ptr(d, C.POINTER(C.c_int8)), d.nbytes,
+                               self._write_flags("write_regions", where, skip_zero))
+
+    def write_regions_device(self, lo_ptr: int, n: int, size, data_ptr: int, n_bytes: int, skip_zero: bool = False, where: Optional[str] = None) -> dict:
+        """write_regions on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 3 int32 and n_bytes >=
+        n * sx * sy * sz int8, any alignment); size = (sx, sy, sz)."""
+        sz = np.ascontiguousarray(size, dtype=np.int32)
+        if sz.shape != (3,):
+            raise VrcError(f"write_regions_device: size must be three integers, got {size}")
+        return self._edit_call(lib.vrc_write_regions_device, C.c_void_p(lo_ptr), int(n), _ptr(sz, _i32p), C.c_void_p(data_ptr), int(n_bytes),
+                               self._write_flags("write_regions_device", where, skip_zero))
 
     # -- octree compaction (vrc_compact_octree, include/vrc.h)
     def compact_octree(self, dry_run: bool = False) -> dict:

@@ -20,6 +20,8 @@
 //                             child block.  The node's new child block (descriptors, then their far slots) is appended; the
 //                             root's level also appends the new root word, right in front of its block.
 // The edit never overwrites a word of the old tree, so the old root still decodes the old scene until the host moves the root.
+// How a wave reads its old brick and how it turns the new one into a subtree live in voxel_edit_emit.hpp: the region edits'
+// brick kernel (region_write.hip) ends in the same code, and the sort, the run lengths and the ancestor pass here serve it too.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -27,45 +29,10 @@
 
 #include "svo_node.hpp"
 #include "voxel_edit.h"
+#include "voxel_edit_emit.hpp"
 #include "vrc_launch.h"
 
 namespace vrc {
-
-namespace {
-
-// bit k of v to bit 3 k (21 bits), and back
-__host__ __device__ inline uint64_t spread3(uint64_t x) {
-    x &= 0x1fffffULL;
-    x = (x | x << 32) & 0x1f00000000ffffULL;
-    x = (x | x << 16) & 0x1f0000ff0000ffULL;
-    x = (x | x << 8) & 0x100f00f00f00f00fULL;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ULL;
-    x = (x | x << 2) & 0x1249249249249249ULL;
-    return x;
-}
-__host__ __device__ inline uint32_t compact3(uint64_t x) {
-    x &= 0x1249249249249249ULL;
-    x = (x ^ (x >> 2)) & 0x10c30c30c30c30c3ULL;
-    x = (x ^ (x >> 4)) & 0x100f00f00f00f00fULL;
-    x = (x ^ (x >> 8)) & 0x1f0000ff0000ffULL;
-    x = (x ^ (x >> 16)) & 0x1f00000000ffffULL;
-    x = (x ^ (x >> 32)) & 0x1fffffULL;
-    return (uint32_t)x;
-}
-
-// first index in [0, n) whose key is not below `key`
-__device__ inline int64_t lower_bound(const uint64_t *keys, int64_t n, uint64_t key) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (keys[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ inline uint64_t leaf_bits_for(unsigned valid, unsigned leaves) { return (uint64_t)((~valid & 0xffu) | leaves); }
-
-}  // namespace
 
 __global__ __launch_bounds__(kEditThreads) void voxel_edit_key_kernel(const EditParams q) {
     const int64_t stride = (int64_t)gridDim.x * kEditThreads;
@@ -118,17 +85,7 @@ __global__ __launch_bounds__(kEditThreads) void voxel_edit_brick_kernel(const Ed
     int64_t first = 0, last = 0;
     if (live) {
         const uint64_t key = q.brick_keys[u];
-        const int ox = (int)(compact3(key) << kReadBrickLog2), oy = (int)(compact3(key >> 1) << kReadBrickLog2), oz = (int)(compact3(key >> 2) << kReadBrickLog2);
-        const int n = q.scene.log2_dim;
-        if (n >= kReadBrickLog2) {
-            uint64_t cur = 0, index = 0;
-            const int state = descend_to_node(q.scene, ox, oy, oz, kReadBrickLog2, cur, index);
-            if (state == 1) old_row = 0x0505050505050505ULL;
-            if (state == 2) old_row = node_row<3>(q.scene, cur, index, ly, lz);
-        } else if (ly < (1 << n) && lz < (1 << n)) {
-            const uint64_t cur = node_entry(q.scene.descriptors, q.scene.root_index, q.scene.descriptors[VRC_IDX(kDescriptors, q.scene.root_index)]);
-            old_row = n == 2 ? node_row<2>(q.scene, cur, q.scene.root_index, ly, lz) : node_row<1>(q.scene, cur, q.scene.root_index, ly, lz);
-        }
+        old_row = edit_old_row(q, key, ly, lz);
         first = lower_bound(q.sorted_keys, q.n, key);
         last = lower_bound(q.sorted_keys, q.n, key + 1);
     }
@@ -149,54 +106,7 @@ __global__ __launch_bounds__(kEditThreads) void voxel_edit_brick_kernel(const Ed
         if (s_owner[wave][v] == (uint32_t)(i - first + 1)) bytes[v] = (int8_t)q.materials[e];
     }
     __syncthreads();
-    // voxels whose material differs after the batch
-    {
-        const uint64_t diff = old_row ^ s_rows[wave][lane];
-        int changed = 0;
-        for (int k = 0; k < 8; k++) changed += ((diff >> (8 * k)) & 0xffULL) ? 1 : 0;
-        for (int d = 32; d >= 1; d >>= 1) changed += __shfl_down(changed, d, 64);
-        if (lane == 0 && changed) atomicAdd(&q.counters[kEditChanged], (unsigned long long)changed);
-    }
-    // the subtree: lane j owns the 2^3 block `lo` of the 4^3 child `hi`
-    const int hi = lane >> 3, lo = lane & 7;
-    const int x2 = ((hi & 1) << 1) | (lo & 1), y2 = (((hi >> 1) & 1) << 1) | ((lo >> 1) & 1), z2 = (((hi >> 2) & 1) << 1) | ((lo >> 2) & 1);
-    uint64_t mats = 0;
-    unsigned valid = 0;
-    for (int s = 0; s < 8; s++) {
-        const uint8_t b = (uint8_t)bytes[(2 * x2 + (s & 1)) + 8 * ((2 * y2 + ((s >> 1) & 1)) + 8 * (2 * z2 + (s >> 2)))];
-        mats |= (uint64_t)b << (8 * s);
-        if (b) valid |= 1u << s;
-    }
-    const uint64_t filled = __ballot(live && valid != 0);         // bit j: block j holds a voxel
-    if (!live) return;
-    unsigned brick_valid = 0;
-    for (int k = 0; k < 8; k++)
-        if ((filled >> (8 * k)) & 0xffULL) brick_valid |= 1u << k;
-    const uint64_t base = q.brick_base + kEditBrickStride * (uint64_t)u;
-    const unsigned n_mid = shallow == 1 ? 0u : (unsigned)__builtin_popcount(brick_valid);
-    const uint64_t below_me = (uint64_t)__builtin_popcountll(filled & ((1ULL << lane) - 1ULL));
-    if (valid) {
-        const uint64_t at = base + n_mid + below_me;
-        q.descriptors[at] = ((uint64_t)valid << 16) | kLeafAll;
-        if (q.attach_lookup) {
-            const uint64_t slot = q.attach_base + kEditBrickAttach * (uint64_t)u + below_me;
-            q.attachments[slot] = mats;
-            q.attach_lookup[at] = (uint32_t)slot;
-        }
-    }
-    const unsigned mid_valid = (unsigned)(filled >> (8 * hi)) & 0xffu;
-    if (lo == 0 && mid_valid && shallow != 1) {
-        const uint64_t at = base + (uint64_t)__builtin_popcount(brick_valid & ((1u << hi) - 1u));
-        q.descriptors[at] = (base + n_mid + below_me - at) | ((uint64_t)mid_valid << 16) | (leaf_bits_for(mid_valid, 0) << 24);
-    }
-    if (lane == 0) {
-        q.rec_masks[u] = brick_valid | ((uint32_t)leaf_bits_for(brick_valid, 0) << 8);
-        q.rec_child[u] = base;
-        // a tree no deeper than a brick: the root is the brick's own word (depth 3, in front of the subtree), its 4^3 child 0
-        // (depth 2) or its 2^3 block 0 (depth 1), which the lanes above have stored at `base` unless it is empty
-        if (shallow == 3) q.descriptors[base - 1] = 1ULL | ((uint64_t)brick_valid << 16) | (leaf_bits_for(brick_valid, 0) << 24);
-        if ((shallow == 2 || shallow == 1) && !filled) q.descriptors[base] = kLeafAll;
-    }
+    edit_emit_brick(q, shallow, u, lane, live, old_row, s_rows[wave]);
 }
 
 __global__ __launch_bounds__(kEditThreads) void voxel_edit_level_kernel(const EditParams q, const EditLevel L) {

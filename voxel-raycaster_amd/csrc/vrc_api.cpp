@@ -28,6 +28,7 @@
 #include "box_sweep.h"
 #include "octree_compact.h"
 #include "raycast_query.h"
+#include "region_write.h"
 #include "voxel_edit.h"
 #include "voxel_read.h"
 #include "vrc_launch.h"
@@ -37,7 +38,7 @@
 #include "index_audit.hpp"
 namespace vrc {
 #define VRC_AUDIT_DECLARE(name) hipError_t audit_publish_##name(const unsigned long long *extent_plus_1); hipError_t audit_collect_##name(audit::Stat *out, unsigned long long *extent_plus_1, int clear);
-VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit) VRC_AUDIT_DECLARE(compact)
+VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit) VRC_AUDIT_DECLARE(compact) VRC_AUDIT_DECLARE(region)
 #undef VRC_AUDIT_DECLARE
 }  // namespace vrc
 #endif
@@ -164,6 +165,10 @@ struct vrc_caster {
     void *d_edit_temp = nullptr; size_t edit_temp_bytes = 0;
     uint64_t *d_edit_levels = nullptr; int64_t edit_level_capacity = 0;
     uint32_t *d_edit_rec_masks = nullptr; uint64_t *d_edit_rec_child = nullptr; int64_t edit_rec_capacity = 0;
+    // vrc_fill_boxes / vrc_write_regions: staging of the host call (boxes or corners, then materials or blocks); the bricks per
+    // operation and their scan.  Everything behind the pairs is the edit's own scratch above.
+    void *d_region_in = nullptr; size_t region_in_bytes = 0;
+    uint64_t *d_region_counts = nullptr; int64_t region_capacity = 0;
 
     // live (retained) host pointers
     const float *cam_dir = nullptr, *cam_pos = nullptr;
@@ -232,7 +237,7 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
 void release_query_staging(vrc_caster *h) {
     if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp &&
         !h->d_sweep_in && !h->d_sweep_rec && !h->d_read_in && !h->d_read_out && !h->d_edit_in && !h->d_edit_keys && !h->d_edit_counters &&
-        !h->d_edit_temp && !h->d_edit_levels && !h->d_edit_rec_masks) return;
+        !h->d_edit_temp && !h->d_edit_levels && !h->d_edit_rec_masks && !h->d_region_in && !h->d_region_counts) return;
     {
         DeviceRestore restore;
         (void)hipSetDevice(h->device);
@@ -248,6 +253,8 @@ void release_query_staging(vrc_caster *h) {
         release(h->d_edit_in); release(h->d_edit_keys); release(h->d_edit_unique); release(h->d_edit_order); release(h->d_edit_counts);
         release(h->d_edit_counters); release(h->d_edit_temp); release(h->d_edit_levels); release(h->d_edit_rec_masks); release(h->d_edit_rec_child);
         h->edit_in_capacity = 0; h->edit_capacity = 0; h->edit_temp_bytes = 0; h->edit_level_capacity = 0; h->edit_rec_capacity = 0;
+        release(h->d_region_in); release(h->d_region_counts);
+        h->region_in_bytes = 0; h->region_capacity = 0;
     }
     (void)hipGetLastError();
 }
@@ -314,7 +321,7 @@ const AuditTu kAuditTus[] = {
     {vrc::audit_publish_boxes, vrc::audit_collect_boxes},     {vrc::audit_publish_query, vrc::audit_collect_query},
     {vrc::audit_publish_boxq, vrc::audit_collect_boxq},       {vrc::audit_publish_sweep, vrc::audit_collect_sweep},
     {vrc::audit_publish_read, vrc::audit_collect_read},       {vrc::audit_publish_edit, vrc::audit_collect_edit},
-    {vrc::audit_publish_compact, vrc::audit_collect_compact},
+    {vrc::audit_publish_compact, vrc::audit_collect_compact}, {vrc::audit_publish_region, vrc::audit_collect_region},
 };
 hipError_t audit_publish(const AuditExtents &x) {
     hipError_t e = hipDeviceSynchronize();
@@ -2390,6 +2397,9 @@ struct EditTimer {
     void add(double *seconds) { float ms = 0.f; if (hipEventElapsedTime(&ms, a, b) == hipSuccess) *seconds += ms * 1e-3; else (void)hipGetLastError(); }
 };
 
+int edit_append(vrc_caster *g, vrc::EditParams &q, vrc::RegionParams *region, int64_t nb, unsigned long long *c, EditTimer &timer, EditStage &st,
+                const char *what);
+
 // One handle's edit up to the commit (current device: g->device; d_pos / d_mat: memory of that device).  The array branch
 // stores in place; the SVO branch appends behind n_desc and leaves the commit to the caller.
 int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_t n, EditStage &st) {
@@ -2440,6 +2450,17 @@ int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_
     // the touched bricks (the last run is the skipped edits'), and from their keys the touched nodes of every level above them
     const int64_t nb = (int64_t)c[vrc::kEditRuns] - (st.skipped > 0 ? 1 : 0);
     if (nb <= 0) return VRC_OK;
+    return edit_append(g, q, nullptr, nb, c, timer, st, "set_voxels");
+}
+
+// What every front end of an SVO edit ends with (the tree's guard is held; q holds the scene, the sorted batch and the counters,
+// d_edit_unique the keys of the nb touched bricks in order, c the counters as read so far): size the appended range, make room,
+// run the brick pass -- the region edits' own when `region` is given, which then takes q as its edit block -- and the ancestor
+// pass of every level, and fill the stage for the commit.
+int edit_append(vrc_caster *g, vrc::EditParams &q, vrc::RegionParams *region, int64_t nb, unsigned long long *c, EditTimer &timer, EditStage &st,
+                const char *what) {
+    vrc_tree *t = g->tree.get();
+    const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);   // levels above the bricks
     std::vector<std::vector<uint64_t>> levels((size_t)above);
     {
         std::vector<uint64_t> below((size_t)nb);
@@ -2463,8 +2484,8 @@ int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_
     const bool have = t->d_attach_lookup && t->d_attach, want = have || c[vrc::kEditMaterials] != 0;
     q.attach_base = have ? std::max<uint64_t>(t->n_attach, 1) : 1;    // (a tree that gets its materials now: slot 0 is eight 5s)
     st.n_attach = want ? q.attach_base + vrc::kEditBrickAttach * (uint64_t)nb : 0;
-    if (st.n_attach > 0xffffffffULL) return fail(g, VRC_ERR_LIMIT, "set_voxels: more than 2^32 attachment slots");
-    if (st.n_desc >= (1ULL << 47)) return fail(g, VRC_ERR_LIMIT, "set_voxels: more than 2^47 descriptors");
+    if (st.n_attach > 0xffffffffULL) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^32 attachment slots", what);
+    if (st.n_desc >= (1ULL << 47)) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^47 descriptors", what);
 
     // room: arrays that cannot take the batch are staged anew and copied device to device; the tree keeps its own until the commit
     size_t free_b = 0, total_b = 0;
@@ -2490,8 +2511,8 @@ int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(g, e == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE, "set_voxels: growing the octree by %llu words failed: %s",
-                    (unsigned long long)st.added, hipGetErrorString(e));
+        return fail(g, e == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE, "%s: growing the octree by %llu words failed: %s",
+                    what, (unsigned long long)st.added, hipGetErrorString(e));
     }
     q.descriptors = st.desc ? st.desc : t->d_desc;
     q.attach_lookup = !want ? nullptr : st.lookup ? st.lookup : t->d_attach_lookup;
@@ -2514,7 +2535,12 @@ int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_
     q.brick_keys = g->d_edit_unique; q.n_bricks = nb;
     q.rec_masks = g->d_edit_rec_masks; q.rec_child = g->d_edit_rec_child;
     HIP_TRY(g, hipEventRecord(timer.a, g->stream));
-    HIP_TRY(g, vrc::launch_edit_bricks(q, g->stream));
+    if (region) {
+        region->edit = q;
+        HIP_TRY(g, vrc::launch_region_bricks(*region, g->stream));
+    } else {
+        HIP_TRY(g, vrc::launch_edit_bricks(q, g->stream));
+    }
     {
         vrc::EditLevel l;
         memset(&l, 0, sizeof(l));
@@ -2530,7 +2556,7 @@ int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_
         }
     }
     HIP_TRY(g, hipEventRecord(timer.b, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(unsigned long long) * vrc::kEditCounters, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(g, hipStreamSynchronize(g->stream));
     timer.add(&st.seconds);
     st.changed = (int64_t)c[vrc::kEditChanged];
@@ -2566,7 +2592,108 @@ void edit_commit(EditStage &st) {
     (void)hipGetLastError();
 }
 
-int edit_run(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, bool on_device, vrc_edit_info *info, const char *what) {
+// A batch of region operations: `first` is the boxes (fill, int32[6 n]) or the corners (paste, int32[3 n]), `second` the materials
+// (int32[n]) or the blocks (n * volume bytes).
+struct RegionBatch {
+    int paste; uint32_t flags; int32_t size[3]; uint64_t volume; const char *what;
+    size_t first_bytes(int64_t n) const { return sizeof(int32_t) * (paste ? 3 : 6) * (size_t)n; }
+    size_t second_bytes(int64_t n) const { return paste ? (size_t)volume * (size_t)n : sizeof(int32_t) * (size_t)n; }
+};
+
+// One handle's region edit up to the commit, as edit_stage: the front end that turns operations into (brick, operation) pairs
+// without enumerating a voxel (region_write.hip), then the map's brick pass or the SVO edit's own tail.
+int region_stage(vrc_caster *g, const RegionBatch &b, const int32_t *d_first, const void *d_second, int64_t n, EditStage &st) {
+    st.h = g; st.ran = true;
+    vrc_tree *t = g->tree.get();
+    std::unique_lock<std::mutex> lock(t->guard);
+    HIP_TRY(g, hipStreamSynchronize(g->stream));                      // a frame in flight finishes first
+    vrc::RegionParams rp;
+    memset(&rp, 0, sizeof(rp));
+    vrc::EditParams &q = rp.edit;
+    bind_scene(g, t, q.scene);
+    q.scene.coarse = nullptr; q.scene.coarse_log2 = 0;                // (the table goes with the edit: every descent starts at the root)
+    const bool svo = q.scene.svo != 0;
+    const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);
+    rp.boxes = d_first; rp.n = n; rp.paste = b.paste; rp.flags = b.flags; rp.volume = b.volume;
+    if (b.paste) rp.data = static_cast<const int8_t *>(d_second); else rp.materials = static_cast<const int32_t *>(d_second);
+    for (int a = 0; a < 3; a++) { rp.size[a] = b.size[a]; rp.lim[a] = q.scene.map_dim[a]; }
+    // the map's rows at z >= dy have an index past the array (dy <= dz: write_check): they are outside the scene
+    if (!svo) rp.lim[2] = std::min(rp.lim[2], rp.lim[1]);
+    for (int a = 0; a < 3; a++) rp.nb[a] = ((int64_t)rp.lim[a] + 7) / 8;
+    int bits = 3 * above;
+    if (!svo)
+        for (bits = 0; bits < 63 && (1ULL << bits) < (uint64_t)(rp.nb[0] * rp.nb[1] * rp.nb[2]); bits++) {}
+    bits = std::max(bits, 1);
+    const bool have = t->d_attach_lookup && t->d_attach;
+    rp.scan_materials = svo && b.paste && !have;
+    q.map = g->d_map;
+    VRC_TRY(grow(g, g->region_capacity, n + 1, {{g->d_region_counts, sizeof(uint64_t) * 2 * (size_t)(n + 1)}}));
+    rp.counts = g->d_region_counts; rp.offsets = g->d_region_counts + (n + 1);
+    if (!g->d_edit_counters) HIP_TRY(g, hipMalloc((void **)&g->d_edit_counters, sizeof(unsigned long long) * vrc::kEditCounters));
+    q.counters = g->d_edit_counters;
+    size_t scan_bytes = 0;
+    HIP_TRY(g, vrc::region_scan(nullptr, &scan_bytes, rp.counts, rp.offsets, n + 1, g->stream));
+    scan_bytes = std::max<size_t>(scan_bytes, 16);
+    VRC_TRY(grow(g, g->edit_temp_bytes, scan_bytes, {{g->d_edit_temp, scan_bytes}}));
+    EditTimer timer;
+    HIP_TRY(g, timer.init());
+    unsigned long long c[vrc::kEditCounters];
+    uint64_t pairs = 0;
+
+    // the bricks every operation overlaps, their scan, and the one read-back the sizes of everything else depend on
+    HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(c), g->stream));
+    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
+    HIP_TRY(g, vrc::launch_region_count(rp, g->stream));
+    if (rp.scan_materials) HIP_TRY(g, vrc::launch_region_materials(rp, g->stream));
+    HIP_TRY(g, vrc::region_scan(g->d_edit_temp, &scan_bytes, rp.counts, rp.offsets, n + 1, g->stream));
+    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(&pairs, rp.offsets + n, sizeof(pairs), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    timer.add(&st.seconds);
+    st.skipped = (int64_t)c[vrc::kEditSkipped];
+    if (pairs == 0) return VRC_OK;
+    if (pairs > (uint64_t)INT32_MAX) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 (brick, operation) pairs", b.what);
+
+    // the pairs, sorted by brick (stable: a brick's operations stay in index order), and the touched bricks in key order
+    const int64_t np = (int64_t)pairs;
+    VRC_TRY(grow(g, g->edit_capacity, np, {{g->d_edit_keys, sizeof(uint64_t) * 2 * (size_t)np}, {g->d_edit_order, sizeof(uint32_t) * 2 * (size_t)np},
+                                           {g->d_edit_unique, sizeof(uint64_t) * (size_t)np}, {g->d_edit_counts, sizeof(uint32_t) * (size_t)np}}));
+    q.n = np;
+    q.keys = g->d_edit_keys; q.order = g->d_edit_order;
+    q.sorted_keys = g->d_edit_keys + np; q.sorted_order = g->d_edit_order + np;
+    size_t sort_bytes = 0, run_bytes = 0;
+    HIP_TRY(g, vrc::edit_sort(nullptr, &sort_bytes, q.keys, g->d_edit_keys + np, q.order, g->d_edit_order + np, np, bits, g->stream));
+    HIP_TRY(g, vrc::edit_runs(nullptr, &run_bytes, q.sorted_keys, np, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
+    const size_t temp_bytes = std::max<size_t>(std::max(sort_bytes, run_bytes), 16);
+    VRC_TRY(grow(g, g->edit_temp_bytes, temp_bytes, {{g->d_edit_temp, temp_bytes}}));
+    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
+    HIP_TRY(g, vrc::launch_region_emit(rp, g->stream));
+    HIP_TRY(g, vrc::edit_sort(g->d_edit_temp, &sort_bytes, q.keys, g->d_edit_keys + np, q.order, g->d_edit_order + np, np, bits, g->stream));
+    HIP_TRY(g, vrc::edit_runs(g->d_edit_temp, &run_bytes, q.sorted_keys, np, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
+    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(c + vrc::kEditRuns, q.counters + vrc::kEditRuns, sizeof(c[0]), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    timer.add(&st.seconds);
+    const int64_t nb = (int64_t)c[vrc::kEditRuns];
+    if (nb <= 0) return VRC_OK;
+    if (svo) return edit_append(g, q, &rp, nb, c, timer, st, b.what);
+
+    // the map: one wave per touched brick of the map, in place
+    q.brick_keys = g->d_edit_unique; q.n_bricks = nb;
+    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
+    HIP_TRY(g, vrc::launch_region_bricks(rp, g->stream));
+    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
+    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(g, hipStreamSynchronize(g->stream));
+    timer.add(&st.seconds);
+    st.changed = (int64_t)c[vrc::kEditChanged];
+    return VRC_OK;
+}
+
+// positions / materials: the batch of vrc_set_voxels; with `region`, its first and second array (RegionBatch)
+int edit_run(vrc_caster *h, const void *positions, const void *materials, int64_t n, bool on_device, vrc_edit_info *info, const char *what,
+             const RegionBatch *region = nullptr) {
     if (info && info->struct_size < sizeof(uint32_t)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: info->struct_size is not set", what);
     vrc_edit_info out;
     memset(&out, 0, sizeof(out));
@@ -2584,8 +2711,15 @@ int edit_run(vrc_caster *h, const int32_t *positions, const int32_t *materials, 
             for (size_t k = 0; k < r && svo; k++) shared = shared || group[k]->tree.get() == g->tree.get();
             if (shared) continue;
             HIP_TRY(h, hipSetDevice(g->device));
-            const int32_t *d_pos = positions, *d_mat = materials;
-            if (!on_device || g->device != h->device) {               // staged: the host's arrays, or rank 0's for a rank on another GPU
+            const int32_t *d_pos = static_cast<const int32_t *>(positions), *d_mat = static_cast<const int32_t *>(materials);
+            const void *d_second = materials;
+            if (region && (!on_device || g->device != h->device)) {
+                const size_t first = (region->first_bytes(n) + 15) & ~(size_t)15, bytes = first + region->second_bytes(n);
+                VRC_TRY(grow(g, g->region_in_bytes, bytes, {{g->d_region_in, bytes}}));
+                HIP_TRY(h, hipMemcpyAsync(g->d_region_in, positions, region->first_bytes(n), hipMemcpyDefault, g->stream));
+                HIP_TRY(h, hipMemcpyAsync(static_cast<char *>(g->d_region_in) + first, materials, region->second_bytes(n), hipMemcpyDefault, g->stream));
+                d_pos = static_cast<const int32_t *>(g->d_region_in); d_second = static_cast<const char *>(g->d_region_in) + first;
+            } else if (!on_device || g->device != h->device) {        // staged: the host's arrays, or rank 0's for a rank on another GPU
                 VRC_TRY(grow(g, g->edit_in_capacity, n, {{g->d_edit_in, sizeof(int32_t) * 4 * (size_t)n}}));
                 HIP_TRY(h, hipMemcpyAsync(g->d_edit_in, positions, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDefault, g->stream));
                 HIP_TRY(h, hipMemcpyAsync(g->d_edit_in + 3 * n, materials, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, g->stream));
@@ -2593,7 +2727,7 @@ int edit_run(vrc_caster *h, const int32_t *positions, const int32_t *materials, 
             } else {
                 VRC_TRY(wait_for_null_stream(g));
             }
-            const int rc = edit_stage(g, d_pos, d_mat, n, *stages.back());
+            const int rc = region ? region_stage(g, *region, d_pos, d_second, n, *stages.back()) : edit_stage(g, d_pos, d_mat, n, *stages.back());
             if (rc != VRC_OK) return g == h ? rc : fail(h, rc, "rank %zu: %s", r, g->error.c_str());
         }
         const EditStage &s0 = *stages[0];
@@ -2643,6 +2777,106 @@ int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_
             return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels_device: positions and materials must be memory the GPU of the handle (device %d) can read", h->device);
     }
     return edit_run(h, static_cast<const int32_t *>(d_positions), static_cast<const int32_t *>(d_materials), n, true, info, "set_voxels_device");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// region edits (vrc_fill_boxes / vrc_write_regions and their _device variants, region_write.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the argument checks of the four calls, then the edit's readiness checks; nothing is launched when one fails
+int write_check(vrc_caster *h, const void *first, const void *second, int64_t n, uint32_t flags, bool paste, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    const uint32_t known = VRC_WRITE_WHERE_EMPTY | VRC_WRITE_WHERE_SOLID | (paste ? VRC_WRITE_SKIP_ZERO : 0u);
+    if (flags & ~known) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~known));
+    if ((flags & VRC_WRITE_WHERE_EMPTY) && (flags & VRC_WRITE_WHERE_SOLID))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: WHERE_EMPTY and WHERE_SOLID exclude each other", what);
+    if (n > 0 && (!first || !second)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null %s", what, paste ? "corners or data" : "boxes or materials");
+    if (n > INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 operations in one batch", what);
+    VRC_TRY(query_check(h, first, n, 0, 0, second, what));
+    if (setting_or(h, "using_octree", 0) == 0) return group_alone_holds_trees(h, what);
+    // the array branch: with dy > dz the frame's index x + dx * (y + dz * z) is not one-to-one over map_dim
+    if (h->map_dim[1] > h->map_dim[2]) return fail(h, VRC_ERR_LIMIT, "%s: a map with dy = %d > dz = %d has voxels that share a byte", what, h->map_dim[1], h->map_dim[2]);
+    for (const vrc_caster *g : h->peers)
+        if (g->map_dim[1] > g->map_dim[2]) return fail(h, VRC_ERR_LIMIT, "%s: a rank's map has dy > dz", what);
+    return VRC_OK;
+}
+
+// size and n_bytes of the pastes, as region_check's: *volume = V
+int write_size_check(vrc_caster *h, int64_t n, const int32_t size[3], size_t n_bytes, uint64_t *volume, const char *what) {
+    if (!size) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null size", what);
+    for (int a = 0; a < 3; a++)
+        if (size[a] < 1) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: size[%d] = %d < 1", what, a, (int)size[a]);
+    size_t bytes = (size_t)size[0];
+    for (uint64_t f : {(uint64_t)size[1], (uint64_t)size[2]}) {
+        if (bytes > SIZE_MAX / f) return fail(h, VRC_ERR_LIMIT, "%s: size[0] * size[1] * size[2] bytes overflows size_t", what);
+        bytes *= (size_t)f;
+    }
+    *volume = bytes;
+    if (n > 0 && bytes > SIZE_MAX / (uint64_t)n) return fail(h, VRC_ERR_LIMIT, "%s: n * size[0] * size[1] * size[2] bytes overflows size_t", what);
+    bytes *= (size_t)std::max<int64_t>(n, 0);
+    if (bytes > (size_t)INT64_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^63 bytes", what);
+    if (n >= 0 && n_bytes < bytes) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: data holds %zu bytes, the regions need %zu", what, n_bytes, bytes);
+    return VRC_OK;
+}
+
+int write_device_pointers(vrc_caster *h, const void *d_first, const void *d_second, bool second_aligned, const char *what) {
+    if (((uintptr_t)d_first & 3u) || (second_aligned && ((uintptr_t)d_second & 3u)))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", what, second_aligned ? "boxes and materials" : "the corners");
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!query_pointer_ok(h, d_first) || !query_pointer_ok(h, d_second))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: the arrays must be memory the GPU of the handle (device %d) can read", what, h->device);
+    return VRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_fill_boxes(vrc_caster *h, const int32_t *boxes, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    VRC_TRY(write_check(h, boxes, materials, n, flags, false, "fill_boxes"));
+    for (int64_t i = 0; i < n; i++) {
+        if (materials[i] < -128 || materials[i] > 127)
+            return fail(h, VRC_ERR_INVALID_ARGUMENT, "fill_boxes: materials[%lld] = %d is outside [-128, 127]", (long long)i, (int)materials[i]);
+        for (int a = 0; a < 3; a++)
+            if (boxes[6 * i + 3 + a] < 1)
+                return fail(h, VRC_ERR_INVALID_ARGUMENT, "fill_boxes: box %lld has size[%d] = %d < 1", (long long)i, a, (int)boxes[6 * i + 3 + a]);
+    }
+    const RegionBatch b{0, flags, {0, 0, 0}, 0, "fill_boxes"};
+    return edit_run(h, boxes, materials, n, false, info, b.what, &b);
+}
+
+int vrc_fill_boxes_device(vrc_caster *h, const void *d_boxes, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    VRC_TRY(write_check(h, d_boxes, d_materials, n, flags, false, "fill_boxes_device"));
+    if (n > 0) VRC_TRY(write_device_pointers(h, d_boxes, d_materials, true, "fill_boxes_device"));
+    const RegionBatch b{0, flags, {0, 0, 0}, 0, "fill_boxes_device"};
+    return edit_run(h, d_boxes, d_materials, n, true, info, b.what, &b);
+}
+
+int vrc_write_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], const int8_t *data, size_t n_bytes, uint32_t flags, vrc_edit_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    uint64_t volume = 0;
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "write_regions: n = %lld < 0", (long long)n);
+    VRC_TRY(write_size_check(h, n, size, n_bytes, &volume, "write_regions"));
+    VRC_TRY(write_check(h, lo, data, n, flags, true, "write_regions"));
+    const RegionBatch b{1, flags, {size[0], size[1], size[2]}, volume, "write_regions"};
+    return edit_run(h, lo, data, n, false, info, b.what, &b);
+}
+
+int vrc_write_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], const void *d_data, size_t n_bytes, uint32_t flags, vrc_edit_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    uint64_t volume = 0;
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "write_regions_device: n = %lld < 0", (long long)n);
+    VRC_TRY(write_size_check(h, n, size, n_bytes, &volume, "write_regions_device"));
+    VRC_TRY(write_check(h, d_lo, d_data, n, flags, true, "write_regions_device"));
+    if (n > 0) VRC_TRY(write_device_pointers(h, d_lo, d_data, false, "write_regions_device"));
+    const RegionBatch b{1, flags, {size[0], size[1], size[2]}, volume, "write_regions_device"};
+    return edit_run(h, d_lo, d_data, n, true, info, b.what, &b);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Everything the host layer (vrc_api.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
 // vrc_api.cpp and by every file that defines one of these functions, so the compiler holds each definition against its
-// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h, voxel_edit.h and octree_compact.h.
+// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h, voxel_edit.h, region_write.h and octree_compact.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@ struct SweepParams;
 struct ReadParams;
 struct EditParams;
 struct EditLevel;
+struct RegionParams;
 struct CompactParams;
 struct CompactLevel;
 
@@ -80,6 +81,13 @@ hipError_t edit_runs(void *temp, size_t *temp_bytes, const uint64_t *sorted_keys
 hipError_t launch_edit_array(const EditParams &q, hipStream_t stream);
 hipError_t launch_edit_bricks(const EditParams &q, hipStream_t stream);
 hipError_t launch_edit_level(const EditParams &q, const EditLevel &level, hipStream_t stream);
+
+// region_write.hip
+hipError_t launch_region_count(const RegionParams &p, hipStream_t stream);
+hipError_t launch_region_materials(const RegionParams &p, hipStream_t stream);
+hipError_t region_scan(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, int64_t n, hipStream_t stream);
+hipError_t launch_region_emit(const RegionParams &p, hipStream_t stream);
+hipError_t launch_region_bricks(const RegionParams &p, hipStream_t stream);
 
 // octree_compact.hip
 hipError_t launch_compact_level(const CompactParams &q, const CompactLevel &level, int pass, hipStream_t stream);
