@@ -585,7 +585,80 @@ def test_compaction_after_a_fill(atlas):
     _paste_and_check(a, dim, want, blo, data, 0, "paste-after-compaction")
 
 
-# ---------------------------------------------------------------------------- 17. the index-audit build
+# ---------------------------------------------------------------------------- 17. one handle, alternating calls
+def _alternating_calls(rng, dim):
+    """[(call, arguments)]: point edits, fills and pastes of growing and shrinking size, which follow each other through the one
+    staging buffer and the one set of scratch buffers a handle has for all of them"""
+    p, pm = er.random_batch(rng, dim, n=1000)
+    q, qm = er.random_batch(rng, dim, n=1000)
+    lo = np.array([[3, 4, 5], [20, -2, 9], [7, 7, 7]], I)
+    size = np.array([[6, 9, 4], [5, 11, 10], [1, 1, 20]], I)
+    blo = np.array([[1, 2, 3], [28, 14, 22]], I)                  # (the second block leaves the scene on x and z)
+    data = rng.choice(np.array([0, 5, 6, 7, -3], np.int8), size=(2, 7, 3, 5))      # two blocks of 5 x 3 x 7 voxels
+    return [("set_voxels", (np.array([[9, 10, 11]], I), np.array([7], I))),
+            ("fill_boxes", (lo, size, np.array([6, 0, -3], I))),
+            ("set_voxels", (p, pm)),
+            ("write_regions", (blo, data)),
+            ("set_voxels", (q[:3], qm[:3])),
+            ("release", ()),
+            ("set_voxels", (q, qm))]
+
+
+def _expanded(call, args, dims):
+    """(replay on a grid, the vrc_set_voxels batch with the same result) of one call with flags = 0"""
+    if call == "set_voxels":
+        return (lambda g: er.replay(g, *args)), args
+    if call == "fill_boxes":
+        return (lambda g: rg.fill(g, *args)), rg.expand_fill(*args, dims)
+    return (lambda g: rg.paste(g, *args)), rg.expand_paste(*args, dims)
+
+
+def test_one_handle_takes_alternating_calls(atlas):
+    dim = 32                                                    # depth 5: two levels above the bricks
+    grid = ch.grid_of(dim, 170)
+    c, twin = ch.caster(atlas, dim, grid), ch.caster(atlas, dim, grid)
+    cur = grid
+    for k, (call, args) in enumerate(_alternating_calls(np.random.default_rng(171), dim)):
+        if call == "release":                                   # frees the staging and the scratch: the next call grows them again
+            assert c.release_viewport() and c.create_viewport(ch.W, ch.H) and c.validate(), c.last_error()
+            continue
+        replay, (p, pm) = _expanded(call, args, (dim,) * 3)
+        cur, skipped, changed = replay(cur)
+        info = getattr(c, call)(*args)
+        print(k, call, info)
+        assert (info["skipped"], info["voxels_changed"]) == (skipped, changed), (k, call, info, skipped, changed)
+        # the arrays: every word, against the replayed grid and against a handle that only ever received point edits
+        desc, root, lookup, attach = ch.state(c)
+        assert np.array_equal(rl.decode(desc, root, dim, lookup, attach), cur.reshape(-1)), (k, call)
+        assert np.array_equal(ch.whole(c, dim), np.pad(cur, 1)), (k, call)
+        ti = twin.set_voxels(p, pm)
+        _same_arrays(c, twin, (k, call))
+        for key in ("voxels_changed", "bricks_touched", "descriptors_added", "n_descriptors", "root_index"):
+            assert info[key] == ti[key], (k, call, key)
+    _rebuilt(c, dim, cur)
+
+
+def test_one_handle_takes_alternating_calls_on_the_array_branch(atlas):
+    dims = (32, 32, 32)
+    rng = np.random.default_rng(172)
+    mp = rng.choice(np.array([0, 0, 5, 6, 1, -2], np.int8), size=32 ** 3)
+    c = _map_caster(atlas, dims, mp, tree_dim=32)
+    cur = _map_grid(c, dims)
+    assert np.array_equal(cur.reshape(-1), mp)
+    tree0, attach0 = c.read_descriptors(), c.read_attachments()
+    for k, (call, args) in enumerate(_alternating_calls(rng, 32)):
+        if call == "release":
+            assert c.release_viewport() and c.create_viewport(64, 48) and c.validate(), c.last_error()
+            continue
+        cur, skipped, changed = _expanded(call, args, dims)[0](cur)
+        info = getattr(c, call)(*args)
+        print(k, call, info)
+        assert (info["skipped"], info["voxels_changed"], info["bricks_touched"], info["descriptors_added"]) == (skipped, changed, 0, 0), (k, call, info)
+        assert np.array_equal(_map_grid(c, dims), cur), (k, call)
+        assert np.array_equal(c.read_descriptors(), tree0) and c.read_attachments() == attach0, "the array branch left the tree alone"
+
+
+# ---------------------------------------------------------------------------- 18. the index-audit build
 def test_audit_build_fills_pastes_and_renders_without_a_violation(tmp_path):
     out = str(tmp_path / "region_audit.json")
     env = dict(os.environ, VRC_LIB_PATH=os.path.join(ROOT, "voxel-raycaster_amd", "libvrc_audit.so"))

@@ -1,4 +1,4 @@
-// Kernel-argument blocks of the octree compaction (vrc_compact_octree, include/vrc.h), shared by the host layer (vrc_api.cpp)
+// Kernel-argument blocks of the octree compaction (vrc_compact_octree, include/vrc.h), shared by the host layer (vrc_scene_edit.cpp)
 // and octree_compact.hip.  The scene is a SceneView (vrc_params.h) of the tree BEFORE the call; the passes read only that tree
 // and store only into the new arrays and the call's own scratch.
 #pragma once

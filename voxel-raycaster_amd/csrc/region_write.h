@@ -1,5 +1,5 @@
 // Kernel-argument block of the region edits (vrc_fill_boxes / vrc_write_regions and their _device variants, include/vrc.h),
-// shared by the host layer (vrc_api.cpp) and region_write.hip.  The front end turns the operations into (brick key, operation)
+// shared by the host layer (vrc_scene_edit.cpp) and region_write.hip.  The front end turns the operations into (brick key, operation)
 // pairs; from the sorted pairs on the edit's own argument block (voxel_edit.h) carries everything, so `edit` is filled the way
 // vrc_set_voxels fills it: sorted_keys / sorted_order / n are the pairs, brick_keys / n_bricks the touched bricks.
 #pragma once

@@ -1,5 +1,5 @@
 // Kernel-argument blocks of the voxel edits (vrc_set_voxels / vrc_set_voxels_device, include/vrc.h), shared by the host layer
-// (vrc_api.cpp) and voxel_edit.hip.  The scene is a SceneView (vrc_params.h) of the tree BEFORE the edit; the edit reads only
+// (vrc_scene_edit.cpp) and voxel_edit.hip.  The scene is a SceneView (vrc_params.h) of the tree BEFORE the edit; the edit reads only
 // words below its n_desc and stores only at and above it.
 #pragma once
 

@@ -9,33 +9,18 @@
 // one host thread: every assign_* / setting call is replicated, the octree is uploaded once and fanned out
 // device-to-device, each rank owns only its row bands of the ray table / frame (vrc_set_row_slice), vrc_compute
 // launches all ranks and returns when all are done, and the read-back calls gather every rank's rows into the
-// caller's frame.  No collective anywhere.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+// caller's frame.  No collective anywhere.  (The calls that change the resident scene: vrc_scene_edit.cpp.)
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-#include <cstring>
-#include <initializer_list>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "../../include/vrc.h"
 #include "box_query.h"
 #include "box_sweep.h"
-#include "octree_compact.h"
 #include "raycast_query.h"
-#include "region_write.h"
-#include "voxel_edit.h"
 #include "voxel_read.h"
-#include "vrc_launch.h"
-#include "vrc_params.h"
+#include "vrc_host.hpp"
 
 #ifdef VRC_INDEX_AUDIT
-#include "index_audit.hpp"
 namespace vrc {
 #define VRC_AUDIT_DECLARE(name) hipError_t audit_publish_##name(const unsigned long long *extent_plus_1); hipError_t audit_collect_##name(audit::Stat *out, unsigned long long *extent_plus_1, int clear);
 VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit) VRC_AUDIT_DECLARE(compact) VRC_AUDIT_DECLARE(region)
@@ -43,159 +28,8 @@ VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_
 }  // namespace vrc
 #endif
 
-namespace {
-
-// the caller's current device, put back on every path out of the scope (a group handle works on rank 0's GPU; a group that lets
-// go of its peers' trees goes on allocating there)
-struct DeviceRestore {
-    int dev = -1;
-    DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) { dev = -1; (void)hipGetLastError(); } }
-    ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
-};
-
-template <class T>
-void release(T *&p) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-}
-
-// What a structure derived from a tree was built for, or failed to be built for: the table's level, the root, the tree's depth ...
-struct TableKey {
-    int log2 = 0; uint64_t root = 0; int depth = 0;
-    bool operator==(const TableKey &o) const { return log2 == o.log2 && root == o.root && depth == o.depth; }
-};
-// ... and for the boxes their form (box_mode) and the levels and records asked for.  (A FAILURE is remembered without the last
-// two: they stay 0 in its key.)
-struct BoxKey {
-    TableKey at; int mode = 0; int64_t levels_asked = 0, records_asked = 0;
-    bool operator==(const BoxKey &o) const { return at == o.at && mode == o.mode && levels_asked == o.levels_asked && records_asked == o.records_asked; }
-};
-// An allocation failed: the frames go on without the structure.  Not retried every frame -- but retried as soon as what was
-// asked for changes (level, root, depth) or the host sets coarse_log2 / empty_boxes again (vrc_setting_add / _set)
-template <class Key>
-struct Derived {
-    Key built, failed;
-    bool gave_up = false;
-    std::string note;                                     // why (cleared when the structure is built after all)
-};
-
-}  // namespace
-
-struct vrc_setting { std::string name, define; int64_t value; };
-
-// One descriptor array resident on one GPU, with its materials and with what the kernels derive from it (the dense table of
-// the tree's top, the empty boxes).  Everything here is a function of the TREE, not of a caster: the handles that render the
-// same array on the same GPU -- the ranks of a group that sit on rank 0's GPU, a handle that adopted another handle's tree
-// (vrc_assign_octree_from) -- hold one Tree between them, so the 1 GB table and the boxes exist once.  The reference never
-// frees or shares anything (CLCaster.cpp:5-12); this is footprint hygiene for trees of BASELINE configs[4]'s size.
-struct vrc_tree {
-    int device = 0;
-    uint64_t *d_desc = nullptr; uint64_t n_desc = 0;
-    uint32_t *d_attach_lookup = nullptr; uint64_t *d_attach = nullptr; uint64_t n_attach = 0;
-    // words allocated, once an edit (vrc_set_voxels) has grown an array beyond what it holds; 0: exactly what it holds
-    uint64_t cap_desc = 0, cap_lookup = 0, cap_attach = 0;
-    uint64_t desc_capacity() const { return cap_desc ? cap_desc : n_desc; }
-    uint64_t lookup_capacity() const { return cap_lookup ? cap_lookup : n_desc; }
-    uint64_t attach_capacity() const { return cap_attach ? cap_attach : std::max<uint64_t>(n_attach, 1); }
-    // derived, built on first use by whichever handle needs them first (guard: handles of several host threads)
-    std::mutex guard;
-    uint64_t *d_coarse = nullptr; Derived<TableKey> coarse;
-    uint32_t *d_boxes = nullptr, *d_box_aux = nullptr; Derived<BoxKey> boxes; double box_build_seconds = 0.0;
-    unsigned long long box_queries_cut = 0;               // region queries of the build that gave up at their budget (boxes smaller than they could be)
-    // box records: one per descriptor (box_mode 1: record = descriptor index) or for the upper levels only (box_mode 2: breadth-first
-    // records, d_box_child = first-child record, d_box_desc / d_box_pos = descriptor and position of a record, kept for the self-check)
-    int box_levels = 0; uint64_t box_records = 0;
-    uint32_t *d_box_child = nullptr; uint64_t *d_box_desc = nullptr, *d_box_pos = nullptr;
-    ~vrc_tree() {
-        {
-            DeviceRestore restore;
-            (void)hipSetDevice(device);
-            release(d_coarse); release(d_boxes); release(d_box_aux); release(d_box_child); release(d_box_desc); release(d_box_pos);
-            release(d_desc); release(d_attach_lookup); release(d_attach);
-        }
-        (void)hipGetLastError();
-    }
-};
-
-struct vrc_caster {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string error;
-
-    // scene buffers (device)
-    int8_t *d_map = nullptr; int32_t map_dim[3] = {0, 0, 0};
-    // the tree (shared, see vrc_tree), attached only once it is complete: "has an octree" is tree != nullptr
-    std::shared_ptr<vrc_tree> tree;
-    bool owns_desc = true;                // false: the tree is another handle's too (a group rank on rank 0's GPU, vrc_assign_octree_from)
-    bool own_copy = false;                // group flag VRC_GROUP_OWN_COPIES: never share, always take the device-to-device copy path
-    int32_t peer_access = -1;             // -1 same GPU as rank 0 / rank 0 itself, 1 direct peer access enabled, 0 the runtime stages the copies
-    void *pinned_stage = nullptr; size_t pinned_stage_bytes = 0;   // read-back staging for a pageable destination (groups)
-    bool last_frame_boxes = false;        // the last enqueued frame was rendered with the tree's empty boxes (its descriptor-read counts are the box traversal's)
-    vrc::LaunchRecord last_launch = {};   // the kernel instance the last enqueued frame was launched with (vrc_last_kernel)
-    bool last_frame_wrote_hits = false;   // d_hits belongs to the last enqueued frame (setting hit_records was on)
-    float *d_viewport = nullptr; float *d_image = nullptr; int32_t *d_hits = nullptr; uint8_t *d_rgba8 = nullptr;
-    uint32_t *d_jump_cache = nullptr, *d_jump_slots = nullptr; int jump_slot_count = 0, jump_slot_threads = 0;   // Euclid tables of the exact closed-form jumps (exact_jump.hpp), per resident block
-    int32_t width = 0, height = 0;
-    bool sliced = false;                  // viewport / image / hits hold only this rank's rows
-    int32_t buffer_rows = 0;              // rows the three buffers hold
-    uint8_t *d_atlas = nullptr; int32_t atlas_w = 0, atlas_h = 0, tile_w = 0, tile_h = 0;
-    unsigned long long *d_partials = nullptr; int partial_blocks = 0;
-    unsigned long long *d_counters = nullptr;
-    int32_t *d_frame = nullptr;           // {bias[3], reads}
-    unsigned int *wd_flag = nullptr;      // host-mapped: raised by the kernel's round watchdog
-    float *d_query_rays = nullptr; int32_t *d_query_out = nullptr; int64_t query_capacity = 0;   // vrc_cast_rays' staging (rays)
-    // vrc_box_intersection: staging of the host call (boxes, records, counts, list), per-box and per-item scratch, scan storage
-    float *d_box_in = nullptr; int32_t *d_box_rec = nullptr; int64_t *d_box_cnt = nullptr; int64_t box_io_capacity = 0;
-    int32_t *d_box_vox = nullptr; size_t box_vox_bytes = 0;
-    void *d_box_plan = nullptr; int64_t *d_box_scan = nullptr; int32_t *d_box_corner = nullptr; int64_t box_capacity = 0;
-    int64_t *d_box_items = nullptr; int64_t box_item_capacity = 0;
-    void *d_box_temp = nullptr; size_t box_temp_bytes = 0;
-    // vrc_sweep_boxes: staging of the host call (sweeps, records); the start test's records, counts and first voxels, the
-    // shape flags and their scan; the number of wave-shaped sweeps (read back with the start test's item totals)
-    float *d_sweep_in = nullptr; int32_t *d_sweep_out = nullptr; int64_t sweep_io_capacity = 0;
-    int32_t *d_sweep_rec = nullptr, *d_sweep_vox = nullptr; int64_t *d_sweep_cnt = nullptr, *d_sweep_scan = nullptr; int64_t sweep_capacity = 0;
-    int64_t sweep_n_big = 0;
-    // vrc_get_voxels / vrc_read_regions: staging of the host calls (positions or corners in, values or bytes out)
-    int32_t *d_read_in = nullptr; int64_t read_in_capacity = 0;
-    void *d_read_out = nullptr; size_t read_out_bytes = 0;
-    // vrc_set_voxels: staging of the host call (positions, materials); keys and edit numbers (unsorted, sorted), the unique keys
-    // and their run lengths; the counters; rocprim's storage; the touched nodes above the bricks (keys) and every touched node's record
-    int32_t *d_edit_in = nullptr; int64_t edit_in_capacity = 0;
-    uint64_t *d_edit_keys = nullptr, *d_edit_unique = nullptr; uint32_t *d_edit_order = nullptr, *d_edit_counts = nullptr; int64_t edit_capacity = 0;
-    unsigned long long *d_edit_counters = nullptr;
-    void *d_edit_temp = nullptr; size_t edit_temp_bytes = 0;
-    uint64_t *d_edit_levels = nullptr; int64_t edit_level_capacity = 0;
-    uint32_t *d_edit_rec_masks = nullptr; uint64_t *d_edit_rec_child = nullptr; int64_t edit_rec_capacity = 0;
-    // vrc_fill_boxes / vrc_write_regions: staging of the host call (boxes or corners, then materials or blocks); the bricks per
-    // operation and their scan.  Everything behind the pairs is the edit's own scratch above.
-    void *d_region_in = nullptr; size_t region_in_bytes = 0;
-    uint64_t *d_region_counts = nullptr; int64_t region_capacity = 0;
-
-    // live (retained) host pointers
-    const float *cam_dir = nullptr, *cam_pos = nullptr;
-    const float *cam_trig = nullptr;      // vrc_assign_camera_trig: the host's own sin / cos of the two angles (nullptr: sinf / cosf here)
-    const float *lights = nullptr; const int32_t *light_count = nullptr;
-
-    std::vector<vrc_setting> settings;    // <= 64 slots (include/CLCaster.h:303)
-
-    int32_t tile_rank = 0, tile_world = 1, band_rows = 8;
-    bool validated = false;
-    int last_blocks = 0;
-    uint64_t frames_enqueued = 0;
-    uint64_t sched_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-
-    // kernel timing
-    struct EvPair { hipEvent_t a, b; };
-    std::vector<EvPair> pending, pool;
-    uint64_t timed_launches = 0; double timed_ms = 0.0;
-
-    // group: this handle is rank 0, peers are ranks 1..n-1
-    std::vector<vrc_caster *> peers;
-    bool is_peer = false;
-};
-
-namespace {
-
-int fail(vrc_caster *h, int code, const char *fmt, ...) {
+// (the helpers vrc_host.hpp declares are defined in its namespace, everything else of this file in the anonymous one)
+int vrc_host::fail(vrc_caster *h, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -205,32 +39,12 @@ int fail(vrc_caster *h, int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(h, call)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            (void)hipGetLastError();      /* reported here: not left behind for a later launch check */ \
-            return fail(h, e_ == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE,    \
-                        "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-        }                                                                                         \
-    } while (0)
+void vrc_host::release_boxes(vrc_tree *t) {
+    release(t->d_boxes); release(t->d_box_aux); release(t->d_box_child); release(t->d_box_desc); release(t->d_box_pos);
+    t->boxes.built = BoxKey{}; t->box_records = 0; t->box_levels = 0;
+}
 
-// a step that reports through the handle's own error text: its failure is the caller's
-#define VRC_TRY(...)                                                                              \
-    do {                                                                                          \
-        const int rc_ = (__VA_ARGS__);                                                            \
-        if (rc_ != VRC_OK) return rc_;                                                            \
-    } while (0)
-
-// replicate a call on every other rank of a group; the first failure is reported through rank 0
-#define FOR_PEERS(h, expr)                                                                        \
-    do {                                                                                          \
-        for (size_t pi_ = 0; pi_ < (h)->peers.size(); pi_++) {                                    \
-            vrc_caster *q = (h)->peers[pi_];                                                      \
-            const int rc_ = (expr);                                                               \
-            if (rc_ != VRC_OK) return fail(h, rc_, "rank %zu: %s", pi_ + 1, q->error.c_str());    \
-        }                                                                                         \
-    } while (0)
+namespace {
 
 // vrc_cast_rays', vrc_box_intersection's, vrc_sweep_boxes', the voxel reads' and the voxel edits' staging and scratch buffers (the caller's device is left
 // as it was)
@@ -265,12 +79,6 @@ void release_viewport_buffers(vrc_caster *h) {
     h->jump_slot_count = 0;
 }
 
-// the tree's empty boxes, in either form
-void release_boxes(vrc_tree *t) {
-    release(t->d_boxes); release(t->d_box_aux); release(t->d_box_child); release(t->d_box_desc); release(t->d_box_pos);
-    t->boxes.built = BoxKey{}; t->box_records = 0; t->box_levels = 0;
-}
-
 // the handle lets go of its tree; the arrays, the table and the boxes are freed with the last handle that holds them
 void release_tree(vrc_caster *h) {
     h->tree.reset();
@@ -298,23 +106,7 @@ void bind_attachments(const vrc_tree *t, const uint32_t *&attach_lookup, const u
 }
 
 #ifdef VRC_INDEX_AUDIT
-// The index-audit build (index_audit.hpp): the extents of the arrays the kernels index, published to the device table of every .hip
-// file from the variables the allocations were made with.  The tables are process-global and per device, so the audit build
-// serialises: the device is drained before the extents change, and the report drains it before it reads.  One host thread.  The
-// host keeps ONE current set of extents and every publish writes all of it to the device that is current, so the ranks of a group on
-// several devices each get the whole set at their own launches; the shrink knob applies to every device alike.
-// (every launch site sets ALL the arrays its kernels may index; what it does not set keeps the extent of the launch before, which those
-// kernels never look at)
-unsigned long long g_audit_shrink[vrc::audit::kArrayCount];       // test-only: taken off the extent of that array (vrc_index_audit_shrink)
-unsigned long long g_audit_current[vrc::audit::kArrayCount];      // extent + 1 as published last; 0: never (counted, not checked)
-struct AuditExtents {
-    unsigned long long e1[vrc::audit::kArrayCount];
-    AuditExtents() { memcpy(e1, g_audit_current, sizeof(e1)); }
-    void set(int id, unsigned long long extent) {
-        const unsigned long long cut = g_audit_shrink[id];
-        e1[id] = (extent > cut ? extent - cut : 0) + 1;
-    }
-};
+// the index-audit build: the extents published last and the table of every .hip file they are published to (vrc_host.hpp)
 struct AuditTu { hipError_t (*publish)(const unsigned long long *); hipError_t (*collect)(vrc::audit::Stat *, unsigned long long *, int); };
 const AuditTu kAuditTus[] = {
     {vrc::audit_publish_raycast, vrc::audit_collect_raycast}, {vrc::audit_publish_jump, vrc::audit_collect_jump},
@@ -323,15 +115,17 @@ const AuditTu kAuditTus[] = {
     {vrc::audit_publish_read, vrc::audit_collect_read},       {vrc::audit_publish_edit, vrc::audit_collect_edit},
     {vrc::audit_publish_compact, vrc::audit_collect_compact}, {vrc::audit_publish_region, vrc::audit_collect_region},
 };
-hipError_t audit_publish(const AuditExtents &x) {
+}  // namespace
+unsigned long long vrc_host::g_audit_shrink[vrc::audit::kArrayCount];
+unsigned long long vrc_host::g_audit_current[vrc::audit::kArrayCount];
+hipError_t vrc_host::audit_publish(const AuditExtents &x) {
     hipError_t e = hipDeviceSynchronize();
     for (const AuditTu &tu : kAuditTus)
         if (e == hipSuccess) e = tu.publish(x.e1);
     memcpy(g_audit_current, x.e1, sizeof(g_audit_current));
     return e;
 }
-// the tree's arrays and what is derived from it
-void audit_tree(AuditExtents &x, const vrc_tree *t) {
+void vrc_host::audit_tree(AuditExtents &x, const vrc_tree *t) {
     using namespace vrc::audit;
     x.set(kDescriptors, t->n_desc); x.set(kFarSlots, t->n_desc);
     const bool attach = t->d_attach_lookup && t->d_attach;
@@ -342,7 +136,7 @@ void audit_tree(AuditExtents &x, const vrc_tree *t) {
     x.set(kBoxes, t->d_boxes ? 8 * t->box_records : 0);
     x.set(kBoxChild, t->d_box_child ? t->box_records : 0);
 }
-#define VRC_AUDIT_PUBLISH(h, x) HIP_TRY(h, audit_publish(x))
+namespace {
 #endif
 
 int prepare_one(vrc_caster *h);           // (below, beside the launch path that shares derive_from_tree with it)
@@ -351,11 +145,6 @@ int find_setting(const vrc_caster *h, const char *name) {
     for (size_t i = 0; i < h->settings.size(); i++)
         if (h->settings[i].name == name) return (int)i;
     return -1;
-}
-
-int64_t setting_or(const vrc_caster *h, const char *name, int64_t dflt) {
-    int i = find_setting(h, name);
-    return i < 0 ? dflt : h->settings[i].value;
 }
 
 // coarse_log2 / empty_boxes / empty_box_records / empty_box_levels set (again) by the host: a build that failed before -- a transient out-of-memory, a level asked too
@@ -367,7 +156,14 @@ void retry_derived(vrc_caster *h, const char *name) {
     h->tree->coarse.gave_up = h->tree->boxes.gave_up = false;
 }
 
-int set_setting(vrc_caster *h, const char *name, const char *define, int64_t value) {
+}  // namespace
+
+int64_t vrc_host::setting_or(const vrc_caster *h, const char *name, int64_t dflt) {
+    int i = find_setting(h, name);
+    return i < 0 ? dflt : h->settings[i].value;
+}
+
+int vrc_host::set_setting(vrc_caster *h, const char *name, const char *define, int64_t value) {
     retry_derived(h, name);
     int i = find_setting(h, name);
     if (i >= 0) { h->settings[i].value = value; return VRC_OK; }
@@ -376,12 +172,14 @@ int set_setting(vrc_caster *h, const char *name, const char *define, int64_t val
     return VRC_OK;
 }
 
-int log2_exact(int64_t v) {
+int vrc_host::log2_exact(int64_t v) {
     if (v < 2 || (v & (v - 1))) return -1;
     int n = 0;
     while ((1LL << n) < v) n++;
     return n;
 }
+
+namespace {
 
 void drain_events(vrc_caster *h) {
     for (auto &p : h->pending) {
@@ -1683,9 +1481,7 @@ int vrc_memory_usage2(vrc_caster *h, int32_t rank, vrc_memory2 *out) {
         snprintf(m.note, sizeof(m.note), "%s%s", t->coarse.note.c_str(), t->boxes.note.c_str());
         m.box_queries_cut = t->d_boxes ? t->box_queries_cut : 0;
     }
-    const uint32_t n = std::min<uint32_t>(out->struct_size, (uint32_t)sizeof(m));
-    m.struct_size = n;
-    memcpy(out, &m, n);
+    write_info(out, m);
     return VRC_OK;
 }
 
@@ -1854,10 +1650,8 @@ int vrc_timing_get(vrc_caster *h, uint64_t *n_launches, double *total_kernel_ms)
 // ---------------------------------------------------------------------------------------------------------------------------
 // batched ray queries (vrc_cast_rays / vrc_cast_rays_device, raycast_query.hip)
 // ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// the argument and readiness checks both calls share; nothing is launched when one fails
-int query_check(vrc_caster *h, const void *rays, int64_t n, int32_t max_steps, uint32_t flags, const void *out, const char *what) {
+// the argument and readiness checks both calls share (and every later query and edit); nothing is launched when one fails
+int vrc_host::query_check(vrc_caster *h, const void *rays, int64_t n, int32_t max_steps, uint32_t flags, const void *out, const char *what) {
     if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
     if (max_steps < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: max_steps = %d < 0", what, (int)max_steps);
     if (flags & ~(uint32_t)VRC_RAY_AS_PIXEL) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_RAY_AS_PIXEL));
@@ -1872,8 +1666,7 @@ int query_check(vrc_caster *h, const void *rays, int64_t n, int32_t max_steps, u
     return VRC_OK;
 }
 
-// device pointers the kernel may dereference: memory of the handle's GPU, managed memory or page-locked host memory
-bool query_pointer_ok(const vrc_caster *h, const void *p) {
+bool vrc_host::query_pointer_ok(const vrc_caster *h, const void *p) {
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof(a));
     const hipError_t e = hipPointerGetAttributes(&a, p);
@@ -1883,8 +1676,7 @@ bool query_pointer_ok(const vrc_caster *h, const void *p) {
     return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged || a.type == hipMemoryTypeUnified;
 }
 
-// work the host queued on the null stream (a torch tensor's fill, say) comes first: the handle's stream does not wait for it by itself
-int wait_for_null_stream(vrc_caster *h) {
+int vrc_host::wait_for_null_stream(vrc_caster *h) {
     hipEvent_t ready = nullptr;
     HIP_TRY(h, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
     hipError_t e = hipEventRecord(ready, nullptr);
@@ -1894,23 +1686,7 @@ int wait_for_null_stream(vrc_caster *h) {
     return VRC_OK;
 }
 
-// Grow device buffers that share one capacity (staging and scratch grow on demand; freed by the release_* calls, destroy).  A frame
-// in flight must not lose buffers it does not use anyway: the stream is drained first.
-struct GrowBuffer {
-    void **p; size_t bytes;
-    template <class T> GrowBuffer(T *&ptr, size_t n) : p((void **)&ptr), bytes(n) {}
-};
-template <class Cap>
-int grow(vrc_caster *h, Cap &have, Cap want, std::initializer_list<GrowBuffer> buffers) {
-    if (have >= want) return VRC_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (const GrowBuffer &b : buffers)
-        if (*b.p) { (void)hipFree(*b.p); *b.p = nullptr; }
-    have = 0;
-    for (const GrowBuffer &b : buffers) HIP_TRY(h, hipMalloc(b.p, b.bytes));
-    have = want;
-    return VRC_OK;
-}
+namespace {
 
 // The tree's table and boxes, if they were built for this root and depth.  The query paths use what vrc_prepare / validate / a
 // frame has built for the tree and never build themselves.  The caller holds t->guard.
@@ -1922,9 +1698,9 @@ bool boxes_for(const vrc_tree *t, uint64_t root, int n) {
     return coarse_for(t, root, n) && t->d_boxes && t->d_box_aux && t->boxes.built.at == t->coarse.built;
 }
 
-// The scene a query runs against (the SceneView of QueryParams, BoxParams and ReadParams), from the handle's settings and its
-// tree.  The caller holds t->guard.
-void bind_scene(const vrc_caster *h, const vrc_tree *t, vrc::SceneView &q) {
+}  // namespace
+
+void vrc_host::bind_scene(const vrc_caster *h, const vrc_tree *t, vrc::SceneView &q) {
     q.svo = setting_or(h, "using_octree", 0) == 0 ? 1 : 0;
     q.descriptors = t->d_desc;
     q.root_index = (uint64_t)setting_or(h, "octree_root_index", 0);
@@ -1951,6 +1727,8 @@ void bind_scene(const vrc_caster *h, const vrc_tree *t, vrc::SceneView &q) {
     }
 #endif
 }
+
+namespace {
 
 // One launch on the handle's stream (current device: h->device).  The tree's guard is held until the kernel is enqueued, as a
 // frame holds it.
@@ -2223,23 +2001,37 @@ int vrc_sweep_boxes_device(vrc_caster *h, const void *d_sweeps, int64_t n, int32
 // ---------------------------------------------------------------------------------------------------------------------------
 // voxel reads (vrc_get_voxels / vrc_read_regions and their _device variants, voxel_read.hip)
 // ---------------------------------------------------------------------------------------------------------------------------
+int vrc_host::size_check(vrc_caster *h, const int32_t size[3], const char *what) {
+    if (!size) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null size", what);
+    for (int a = 0; a < 3; a++)
+        if (size[a] < 1) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: size[%d] = %d < 1", what, a, (int)size[a]);
+    return VRC_OK;
+}
+
+int vrc_host::volume_check(vrc_caster *h, int64_t n, const int32_t size[3], size_t n_bytes, const char *holder, uint64_t *volume, size_t *total,
+                           const char *what) {
+    size_t bytes = (size_t)size[0];
+    for (uint64_t f : {(uint64_t)size[1], (uint64_t)size[2]}) {
+        if (bytes > SIZE_MAX / f) return fail(h, VRC_ERR_LIMIT, "%s: %ssize[0] * size[1] * size[2] bytes overflows size_t", what, volume ? "" : "n * ");
+        bytes *= (size_t)f;
+    }
+    if (volume) *volume = bytes;
+    if (n > 0 && bytes > SIZE_MAX / (uint64_t)n) return fail(h, VRC_ERR_LIMIT, "%s: n * size[0] * size[1] * size[2] bytes overflows size_t", what);
+    bytes *= (size_t)n;
+    if (bytes > (size_t)INT64_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^63 bytes", what);      // (the kernels count their waves in int64)
+    if (n_bytes < bytes) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: %s holds %zu bytes, the regions need %zu", what, holder, n_bytes, bytes);
+    *total = bytes;
+    return VRC_OK;
+}
+
 namespace {
 
 // the argument checks of the region reads, then the readiness checks of the ray queries; *total = n V, the bytes the call writes
 int region_check(vrc_caster *h, const void *lo, int64_t n, const int32_t size[3], const void *out, size_t n_bytes, size_t *total, const char *what) {
     if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
-    if (!size) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null size", what);
-    for (int a = 0; a < 3; a++)
-        if (size[a] < 1) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: size[%d] = %d < 1", what, a, (int)size[a]);
+    VRC_TRY(size_check(h, size, what));
     if (n > 0 && (!lo || !out)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null corners or output", what);
-    size_t bytes = (size_t)size[0];
-    for (uint64_t f : {(uint64_t)size[1], (uint64_t)size[2], (uint64_t)n}) {
-        if (f != 0 && bytes > SIZE_MAX / f) return fail(h, VRC_ERR_LIMIT, "%s: n * size[0] * size[1] * size[2] bytes overflows size_t", what);
-        bytes *= (size_t)f;
-    }
-    if (bytes > (size_t)INT64_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^63 bytes", what);      // (the kernel counts its waves in int64)
-    if (n_bytes < bytes) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: output holds %zu bytes, the regions need %zu", what, n_bytes, bytes);
-    *total = bytes;
+    VRC_TRY(volume_check(h, n, size, n_bytes, "output", nullptr, total, what));
     return query_check(h, lo, n, 0, 0, out, what);
 }
 
@@ -2325,803 +2117,6 @@ int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const in
     int rc = region_check(h, d_lo, n, size, d_out, n_bytes, &total, "read_regions_device");
     if (rc != VRC_OK || n == 0) return rc;
     return read_device(h, d_lo, n, size, d_out, "read_regions_device");
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// voxel edits (vrc_set_voxels / vrc_set_voxels_device, voxel_edit.hip)
-// ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// a holder of the tree outside this group would keep rendering from the old root: its setting cannot be moved from here
-int group_alone_holds_trees(vrc_caster *h, const char *what) {
-    std::vector<const vrc_caster *> group{h};
-    group.insert(group.end(), h->peers.begin(), h->peers.end());
-    for (const vrc_caster *g : group) {
-        if (!g->tree) return fail(h, VRC_ERR_NOT_READY, "%s: a rank of the group has no octree", what);
-        long inside = 0;
-        for (const vrc_caster *o : group) inside += o->tree.get() == g->tree.get() ? 1 : 0;
-        if (g->tree.use_count() > inside)
-            return fail(h, VRC_ERR_LIMIT, "%s: the tree is also held by a handle outside this group (vrc_assign_octree_from); its root cannot be moved from here", what);
-    }
-    return VRC_OK;
-}
-
-// the argument checks of both calls, then the readiness checks of the ray queries; nothing is launched when one fails
-int edit_check(vrc_caster *h, const void *positions, const void *materials, int64_t n, uint32_t flags, const char *what) {
-    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
-    if (flags) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)flags);
-    if (n > 0 && (!positions || !materials)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null positions or materials", what);
-    if (n > INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 edits in one batch", what);
-    VRC_TRY(query_check(h, positions, n, 0, 0, materials, what));
-    if (setting_or(h, "using_octree", 0) != 0) return VRC_OK;
-    return group_alone_holds_trees(h, what);
-}
-
-// What one handle's edit has prepared and edit_commit installs.  Until then the tree is what it was: the appended words lie
-// behind n_desc, in the tree's own arrays where they had room and in the arrays staged here where they had not.
-struct EditStage {
-    vrc_caster *h = nullptr;
-    bool ran = false, commit = false;
-    int64_t skipped = 0, changed = 0, bricks = 0;
-    uint64_t added = 0, n_desc = 0, root = 0, n_attach = 0;
-    double seconds = 0.0;
-    uint64_t *desc = nullptr; uint32_t *lookup = nullptr; uint64_t *attach = nullptr;       // replace the tree's at the commit
-    uint64_t cap_desc = 0, cap_lookup = 0, cap_attach = 0;
-    EditStage() = default;
-    EditStage(const EditStage &) = delete;
-    EditStage &operator=(const EditStage &) = delete;
-    ~EditStage() {
-        if (!desc && !lookup && !attach) return;
-        DeviceRestore restore;
-        (void)hipSetDevice(h->device);
-        release(desc); release(lookup); release(attach);
-        (void)hipGetLastError();
-    }
-};
-
-// words to allocate beyond `need` when an array has to grow (setting edit_reserve; -1: an eighth of the need, at least 4096 words,
-// at most a sixteenth of the device memory that is free)
-uint64_t edit_reserve_for(const vrc_caster *h, uint64_t need, size_t elem_bytes, size_t free_bytes) {
-    const int64_t asked = setting_or(h, "edit_reserve", -1);
-    if (asked >= 0) return (uint64_t)asked;
-    return std::min<uint64_t>(std::max<uint64_t>(need / 8, 4096), (uint64_t)(free_bytes / 16) / elem_bytes);
-}
-
-// device time between two events of the handle's stream, added to *seconds (the stream has been waited for)
-struct EditTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EditTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init() { hipError_t e = hipEventCreate(&a); return e == hipSuccess ? hipEventCreate(&b) : e; }
-    void add(double *seconds) { float ms = 0.f; if (hipEventElapsedTime(&ms, a, b) == hipSuccess) *seconds += ms * 1e-3; else (void)hipGetLastError(); }
-};
-
-int edit_append(vrc_caster *g, vrc::EditParams &q, vrc::RegionParams *region, int64_t nb, unsigned long long *c, EditTimer &timer, EditStage &st,
-                const char *what);
-
-// One handle's edit up to the commit (current device: g->device; d_pos / d_mat: memory of that device).  The array branch
-// stores in place; the SVO branch appends behind n_desc and leaves the commit to the caller.
-int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_t n, EditStage &st) {
-    st.h = g; st.ran = true;
-    vrc_tree *t = g->tree.get();
-    std::unique_lock<std::mutex> lock(t->guard);
-    HIP_TRY(g, hipStreamSynchronize(g->stream));                      // a frame in flight finishes first
-    vrc::EditParams q;
-    memset(&q, 0, sizeof(q));
-    bind_scene(g, t, q.scene);
-    q.scene.coarse = nullptr; q.scene.coarse_log2 = 0;                // (the table goes with the edit: every descent starts at the root)
-    const bool svo = q.scene.svo != 0;
-    const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);   // levels above the bricks
-    int bits = 3 * above;
-    if (!svo)
-        for (bits = 0; bits < 63 && (1ULL << bits) <= q.scene.map_bytes; bits++) {}
-    q.sentinel = svo ? 1ULL << bits : q.scene.map_bytes;
-    q.positions = d_pos; q.materials = d_mat; q.n = n;
-    q.map = g->d_map;
-    VRC_TRY(grow(g, g->edit_capacity, n, {{g->d_edit_keys, sizeof(uint64_t) * 2 * (size_t)n}, {g->d_edit_order, sizeof(uint32_t) * 2 * (size_t)n},
-                                          {g->d_edit_unique, sizeof(uint64_t) * (size_t)n}, {g->d_edit_counts, sizeof(uint32_t) * (size_t)n}}));
-    if (!g->d_edit_counters) HIP_TRY(g, hipMalloc((void **)&g->d_edit_counters, sizeof(unsigned long long) * vrc::kEditCounters));
-    q.keys = g->d_edit_keys; q.order = g->d_edit_order;
-    q.sorted_keys = g->d_edit_keys + n; q.sorted_order = g->d_edit_order + n;
-    q.counters = g->d_edit_counters;
-    size_t sort_bytes = 0, run_bytes = 0;
-    HIP_TRY(g, vrc::edit_sort(nullptr, &sort_bytes, q.keys, g->d_edit_keys + n, q.order, g->d_edit_order + n, n, bits + 1, g->stream));
-    HIP_TRY(g, vrc::edit_runs(nullptr, &run_bytes, q.sorted_keys, n, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
-    const size_t temp_bytes = std::max<size_t>(std::max(sort_bytes, run_bytes), 16);
-    VRC_TRY(grow(g, g->edit_temp_bytes, temp_bytes, {{g->d_edit_temp, temp_bytes}}));
-    EditTimer timer;
-    HIP_TRY(g, timer.init());
-    unsigned long long c[vrc::kEditCounters];
-
-    HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(c), g->stream));
-    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
-    HIP_TRY(g, vrc::launch_edit_keys(q, g->stream));
-    HIP_TRY(g, vrc::edit_sort(g->d_edit_temp, &sort_bytes, q.keys, g->d_edit_keys + n, q.order, g->d_edit_order + n, n, bits + 1, g->stream));
-    if (svo) HIP_TRY(g, vrc::edit_runs(g->d_edit_temp, &run_bytes, q.sorted_keys, n, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
-    else HIP_TRY(g, vrc::launch_edit_array(q, g->stream));
-    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-    timer.add(&st.seconds);
-    st.skipped = (int64_t)c[vrc::kEditSkipped];
-    if (!svo) { st.changed = (int64_t)c[vrc::kEditChanged]; return VRC_OK; }
-
-    // the touched bricks (the last run is the skipped edits'), and from their keys the touched nodes of every level above them
-    const int64_t nb = (int64_t)c[vrc::kEditRuns] - (st.skipped > 0 ? 1 : 0);
-    if (nb <= 0) return VRC_OK;
-    return edit_append(g, q, nullptr, nb, c, timer, st, "set_voxels");
-}
-
-// What every front end of an SVO edit ends with (the tree's guard is held; q holds the scene, the sorted batch and the counters,
-// d_edit_unique the keys of the nb touched bricks in order, c the counters as read so far): size the appended range, make room,
-// run the brick pass -- the region edits' own when `region` is given, which then takes q as its edit block -- and the ancestor
-// pass of every level, and fill the stage for the commit.
-int edit_append(vrc_caster *g, vrc::EditParams &q, vrc::RegionParams *region, int64_t nb, unsigned long long *c, EditTimer &timer, EditStage &st,
-                const char *what) {
-    vrc_tree *t = g->tree.get();
-    const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);   // levels above the bricks
-    std::vector<std::vector<uint64_t>> levels((size_t)above);
-    {
-        std::vector<uint64_t> below((size_t)nb);
-        HIP_TRY(g, hipMemcpy(below.data(), g->d_edit_unique, sizeof(uint64_t) * (size_t)nb, hipMemcpyDeviceToHost));
-        for (int j = 0; j < above; j++) {
-            std::vector<uint64_t> &here = levels[(size_t)j];
-            for (uint64_t k : (j ? levels[(size_t)j - 1] : below))
-                if (here.empty() || here.back() != k >> 3) here.push_back(k >> 3);
-        }
-    }
-    int64_t ancestors = 0;
-    for (const auto &l : levels) ancestors += (int64_t)l.size();
-    // the appended range: [a root word in front of a depth-3 brick] the bricks, the levels from the bricks' parents up, the
-    // root word in front of the root level's block
-    const uint64_t first = t->n_desc;
-    st.added = vrc::kEditBrickStride * (uint64_t)nb + vrc::kEditNodeStride * (uint64_t)ancestors + (nlog >= vrc::kReadBrickLog2 ? 1 : 0);
-    st.bricks = nb;
-    st.n_desc = first + st.added;
-    q.brick_base = first + (nlog == vrc::kReadBrickLog2 ? 1 : 0);
-    st.root = above ? st.n_desc - vrc::kEditNodeStride - 1 : first;
-    const bool have = t->d_attach_lookup && t->d_attach, want = have || c[vrc::kEditMaterials] != 0;
-    q.attach_base = have ? std::max<uint64_t>(t->n_attach, 1) : 1;    // (a tree that gets its materials now: slot 0 is eight 5s)
-    st.n_attach = want ? q.attach_base + vrc::kEditBrickAttach * (uint64_t)nb : 0;
-    if (st.n_attach > 0xffffffffULL) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^32 attachment slots", what);
-    if (st.n_desc >= (1ULL << 47)) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^47 descriptors", what);
-
-    // room: arrays that cannot take the batch are staged anew and copied device to device; the tree keeps its own until the commit
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-    auto staged = [&](auto *&p, uint64_t &cap, uint64_t need, size_t elem) -> hipError_t {
-        cap = need + edit_reserve_for(g, need, elem, free_b);
-        return hipMalloc((void **)&p, cap * elem);
-    };
-    hipError_t e = hipSuccess;
-    if (st.n_desc > t->desc_capacity()) {
-        e = staged(st.desc, st.cap_desc, st.n_desc, sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(st.desc, t->d_desc, first * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream);
-    }
-    if (e == hipSuccess && want && (!have || st.n_desc > t->lookup_capacity())) {
-        e = staged(st.lookup, st.cap_lookup, st.n_desc, sizeof(uint32_t));
-        if (e == hipSuccess) e = have ? hipMemcpyAsync(st.lookup, t->d_attach_lookup, first * sizeof(uint32_t), hipMemcpyDeviceToDevice, g->stream)
-                                      : hipMemsetAsync(st.lookup, 0, first * sizeof(uint32_t), g->stream);
-    }
-    if (e == hipSuccess && want && (!have || st.n_attach > t->attach_capacity())) {
-        e = staged(st.attach, st.cap_attach, st.n_attach, sizeof(uint64_t));
-        if (e == hipSuccess) e = have ? hipMemcpyAsync(st.attach, t->d_attach, q.attach_base * sizeof(uint64_t), hipMemcpyDeviceToDevice, g->stream)
-                                      : hipMemsetAsync(st.attach, 0x05, sizeof(uint64_t), g->stream);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(g, e == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE, "%s: growing the octree by %llu words failed: %s",
-                    what, (unsigned long long)st.added, hipGetErrorString(e));
-    }
-    q.descriptors = st.desc ? st.desc : t->d_desc;
-    q.attach_lookup = !want ? nullptr : st.lookup ? st.lookup : t->d_attach_lookup;
-    q.attachments = !want ? nullptr : st.attach ? st.attach : t->d_attach;
-    HIP_TRY(g, hipMemsetAsync(q.descriptors + first, 0, st.added * sizeof(uint64_t), g->stream));     // (what no pass stores stays zero)
-    if (want) {
-        HIP_TRY(g, hipMemsetAsync(q.attach_lookup + first, 0, st.added * sizeof(uint32_t), g->stream));
-        HIP_TRY(g, hipMemsetAsync(q.attachments + q.attach_base, 0, (st.n_attach - q.attach_base) * sizeof(uint64_t), g->stream));
-    }
-    VRC_TRY(grow(g, g->edit_rec_capacity, nb + ancestors, {{g->d_edit_rec_masks, sizeof(uint32_t) * (size_t)(nb + ancestors)},
-                                                           {g->d_edit_rec_child, sizeof(uint64_t) * (size_t)(nb + ancestors)}}));
-    if (ancestors) VRC_TRY(grow(g, g->edit_level_capacity, ancestors, {{g->d_edit_levels, sizeof(uint64_t) * (size_t)ancestors}}));
-    {
-        int64_t at = 0;
-        for (const auto &l : levels) {
-            HIP_TRY(g, hipMemcpyAsync(g->d_edit_levels + at, l.data(), sizeof(uint64_t) * l.size(), hipMemcpyHostToDevice, g->stream));
-            at += (int64_t)l.size();
-        }
-    }
-    q.brick_keys = g->d_edit_unique; q.n_bricks = nb;
-    q.rec_masks = g->d_edit_rec_masks; q.rec_child = g->d_edit_rec_child;
-    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
-    if (region) {
-        region->edit = q;
-        HIP_TRY(g, vrc::launch_region_bricks(*region, g->stream));
-    } else {
-        HIP_TRY(g, vrc::launch_edit_bricks(q, g->stream));
-    }
-    {
-        vrc::EditLevel l;
-        memset(&l, 0, sizeof(l));
-        l.below_keys = g->d_edit_unique; l.below_count = nb; l.rec_below = 0;
-        l.keys = g->d_edit_levels; l.rec_here = nb;
-        l.base = first + vrc::kEditBrickStride * (uint64_t)nb;
-        for (int j = 0; j < above; j++) {
-            l.count = (int64_t)levels[(size_t)j].size();
-            l.r = vrc::kReadBrickLog2 + 1 + j; l.root = j == above - 1 ? 1 : 0;
-            HIP_TRY(g, vrc::launch_edit_level(q, l, g->stream));
-            l.below_keys = l.keys; l.below_count = l.count; l.rec_below = l.rec_here;
-            l.keys += l.count; l.rec_here += l.count; l.base += vrc::kEditNodeStride * (uint64_t)l.count;
-        }
-    }
-    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(unsigned long long) * vrc::kEditCounters, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-    timer.add(&st.seconds);
-    st.changed = (int64_t)c[vrc::kEditChanged];
-    st.commit = st.changed != 0;              // a batch that changes no voxel appends nothing: the words behind n_desc are simply not taken
-    return VRC_OK;
-}
-
-// The last step: the staged arrays replace the tree's (the old ones are freed once the device is idle: hipFree waits), the
-// appended words are taken, what was derived from the old tree goes, and the handle's root moves.
-void edit_commit(EditStage &st) {
-    vrc_caster *g = st.h;
-    vrc_tree *t = g->tree.get();
-    std::lock_guard<std::mutex> lock(t->guard);
-    (void)hipSetDevice(g->device);
-    (void)hipStreamSynchronize(g->stream);
-    auto install = [](auto *&mine, auto *&staged, uint64_t &cap, uint64_t staged_cap) {
-        if (!staged) return;
-        auto *old = mine;
-        mine = staged; cap = staged_cap; staged = nullptr;
-        if (old) (void)hipFree(old);
-    };
-    install(t->d_desc, st.desc, t->cap_desc, st.cap_desc);
-    install(t->d_attach_lookup, st.lookup, t->cap_lookup, st.cap_lookup);
-    install(t->d_attach, st.attach, t->cap_attach, st.cap_attach);
-    if (!t->cap_desc) t->cap_desc = t->n_desc;                        // (the capacities are what is allocated, from here on)
-    if (t->d_attach_lookup && !t->cap_lookup) t->cap_lookup = t->n_desc;
-    if (t->d_attach && !t->cap_attach) t->cap_attach = std::max<uint64_t>(t->n_attach, 1);
-    t->n_desc = st.n_desc;
-    if (st.n_attach) t->n_attach = st.n_attach;
-    // the coarse table and the empty boxes describe the old tree: vrc_prepare / vrc_validate / the next frame build them again
-    release(t->d_coarse); t->coarse.built = TableKey{};
-    release_boxes(t);
-    (void)hipGetLastError();
-}
-
-// A batch of region operations: `first` is the boxes (fill, int32[6 n]) or the corners (paste, int32[3 n]), `second` the materials
-// (int32[n]) or the blocks (n * volume bytes).
-struct RegionBatch {
-    int paste; uint32_t flags; int32_t size[3]; uint64_t volume; const char *what;
-    size_t first_bytes(int64_t n) const { return sizeof(int32_t) * (paste ? 3 : 6) * (size_t)n; }
-    size_t second_bytes(int64_t n) const { return paste ? (size_t)volume * (size_t)n : sizeof(int32_t) * (size_t)n; }
-};
-
-// One handle's region edit up to the commit, as edit_stage: the front end that turns operations into (brick, operation) pairs
-// without enumerating a voxel (region_write.hip), then the map's brick pass or the SVO edit's own tail.
-int region_stage(vrc_caster *g, const RegionBatch &b, const int32_t *d_first, const void *d_second, int64_t n, EditStage &st) {
-    st.h = g; st.ran = true;
-    vrc_tree *t = g->tree.get();
-    std::unique_lock<std::mutex> lock(t->guard);
-    HIP_TRY(g, hipStreamSynchronize(g->stream));                      // a frame in flight finishes first
-    vrc::RegionParams rp;
-    memset(&rp, 0, sizeof(rp));
-    vrc::EditParams &q = rp.edit;
-    bind_scene(g, t, q.scene);
-    q.scene.coarse = nullptr; q.scene.coarse_log2 = 0;                // (the table goes with the edit: every descent starts at the root)
-    const bool svo = q.scene.svo != 0;
-    const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);
-    rp.boxes = d_first; rp.n = n; rp.paste = b.paste; rp.flags = b.flags; rp.volume = b.volume;
-    if (b.paste) rp.data = static_cast<const int8_t *>(d_second); else rp.materials = static_cast<const int32_t *>(d_second);
-    for (int a = 0; a < 3; a++) { rp.size[a] = b.size[a]; rp.lim[a] = q.scene.map_dim[a]; }
-    // the map's rows at z >= dy have an index past the array (dy <= dz: write_check): they are outside the scene
-    if (!svo) rp.lim[2] = std::min(rp.lim[2], rp.lim[1]);
-    for (int a = 0; a < 3; a++) rp.nb[a] = ((int64_t)rp.lim[a] + 7) / 8;
-    int bits = 3 * above;
-    if (!svo)
-        for (bits = 0; bits < 63 && (1ULL << bits) < (uint64_t)(rp.nb[0] * rp.nb[1] * rp.nb[2]); bits++) {}
-    bits = std::max(bits, 1);
-    const bool have = t->d_attach_lookup && t->d_attach;
-    rp.scan_materials = svo && b.paste && !have;
-    q.map = g->d_map;
-    VRC_TRY(grow(g, g->region_capacity, n + 1, {{g->d_region_counts, sizeof(uint64_t) * 2 * (size_t)(n + 1)}}));
-    rp.counts = g->d_region_counts; rp.offsets = g->d_region_counts + (n + 1);
-    if (!g->d_edit_counters) HIP_TRY(g, hipMalloc((void **)&g->d_edit_counters, sizeof(unsigned long long) * vrc::kEditCounters));
-    q.counters = g->d_edit_counters;
-    size_t scan_bytes = 0;
-    HIP_TRY(g, vrc::region_scan(nullptr, &scan_bytes, rp.counts, rp.offsets, n + 1, g->stream));
-    scan_bytes = std::max<size_t>(scan_bytes, 16);
-    VRC_TRY(grow(g, g->edit_temp_bytes, scan_bytes, {{g->d_edit_temp, scan_bytes}}));
-    EditTimer timer;
-    HIP_TRY(g, timer.init());
-    unsigned long long c[vrc::kEditCounters];
-    uint64_t pairs = 0;
-
-    // the bricks every operation overlaps, their scan, and the one read-back the sizes of everything else depend on
-    HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(c), g->stream));
-    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
-    HIP_TRY(g, vrc::launch_region_count(rp, g->stream));
-    if (rp.scan_materials) HIP_TRY(g, vrc::launch_region_materials(rp, g->stream));
-    HIP_TRY(g, vrc::region_scan(g->d_edit_temp, &scan_bytes, rp.counts, rp.offsets, n + 1, g->stream));
-    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(&pairs, rp.offsets + n, sizeof(pairs), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-    timer.add(&st.seconds);
-    st.skipped = (int64_t)c[vrc::kEditSkipped];
-    if (pairs == 0) return VRC_OK;
-    if (pairs > (uint64_t)INT32_MAX) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 (brick, operation) pairs", b.what);
-
-    // the pairs, sorted by brick (stable: a brick's operations stay in index order), and the touched bricks in key order
-    const int64_t np = (int64_t)pairs;
-    VRC_TRY(grow(g, g->edit_capacity, np, {{g->d_edit_keys, sizeof(uint64_t) * 2 * (size_t)np}, {g->d_edit_order, sizeof(uint32_t) * 2 * (size_t)np},
-                                           {g->d_edit_unique, sizeof(uint64_t) * (size_t)np}, {g->d_edit_counts, sizeof(uint32_t) * (size_t)np}}));
-    q.n = np;
-    q.keys = g->d_edit_keys; q.order = g->d_edit_order;
-    q.sorted_keys = g->d_edit_keys + np; q.sorted_order = g->d_edit_order + np;
-    size_t sort_bytes = 0, run_bytes = 0;
-    HIP_TRY(g, vrc::edit_sort(nullptr, &sort_bytes, q.keys, g->d_edit_keys + np, q.order, g->d_edit_order + np, np, bits, g->stream));
-    HIP_TRY(g, vrc::edit_runs(nullptr, &run_bytes, q.sorted_keys, np, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
-    const size_t temp_bytes = std::max<size_t>(std::max(sort_bytes, run_bytes), 16);
-    VRC_TRY(grow(g, g->edit_temp_bytes, temp_bytes, {{g->d_edit_temp, temp_bytes}}));
-    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
-    HIP_TRY(g, vrc::launch_region_emit(rp, g->stream));
-    HIP_TRY(g, vrc::edit_sort(g->d_edit_temp, &sort_bytes, q.keys, g->d_edit_keys + np, q.order, g->d_edit_order + np, np, bits, g->stream));
-    HIP_TRY(g, vrc::edit_runs(g->d_edit_temp, &run_bytes, q.sorted_keys, np, g->d_edit_unique, g->d_edit_counts, q.counters + vrc::kEditRuns, g->stream));
-    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(c + vrc::kEditRuns, q.counters + vrc::kEditRuns, sizeof(c[0]), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-    timer.add(&st.seconds);
-    const int64_t nb = (int64_t)c[vrc::kEditRuns];
-    if (nb <= 0) return VRC_OK;
-    if (svo) return edit_append(g, q, &rp, nb, c, timer, st, b.what);
-
-    // the map: one wave per touched brick of the map, in place
-    q.brick_keys = g->d_edit_unique; q.n_bricks = nb;
-    HIP_TRY(g, hipEventRecord(timer.a, g->stream));
-    HIP_TRY(g, vrc::launch_region_bricks(rp, g->stream));
-    HIP_TRY(g, hipEventRecord(timer.b, g->stream));
-    HIP_TRY(g, hipMemcpyAsync(c, q.counters, sizeof(c), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(g, hipStreamSynchronize(g->stream));
-    timer.add(&st.seconds);
-    st.changed = (int64_t)c[vrc::kEditChanged];
-    return VRC_OK;
-}
-
-// positions / materials: the batch of vrc_set_voxels; with `region`, its first and second array (RegionBatch)
-int edit_run(vrc_caster *h, const void *positions, const void *materials, int64_t n, bool on_device, vrc_edit_info *info, const char *what,
-             const RegionBatch *region = nullptr) {
-    if (info && info->struct_size < sizeof(uint32_t)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: info->struct_size is not set", what);
-    vrc_edit_info out;
-    memset(&out, 0, sizeof(out));
-    const bool svo = setting_or(h, "using_octree", 0) == 0;
-    DeviceRestore restore;
-    if (n > 0) {
-        std::vector<vrc_caster *> group{h};
-        group.insert(group.end(), h->peers.begin(), h->peers.end());
-        std::vector<std::unique_ptr<EditStage>> stages;
-        // every rank stages its edit (a rank that shares an earlier rank's tree has nothing to do), then all of them commit
-        for (size_t r = 0; r < group.size(); r++) {
-            vrc_caster *g = group[r];
-            stages.emplace_back(new EditStage());
-            bool shared = false;
-            for (size_t k = 0; k < r && svo; k++) shared = shared || group[k]->tree.get() == g->tree.get();
-            if (shared) continue;
-            HIP_TRY(h, hipSetDevice(g->device));
-            const int32_t *d_pos = static_cast<const int32_t *>(positions), *d_mat = static_cast<const int32_t *>(materials);
-            const void *d_second = materials;
-            if (region && (!on_device || g->device != h->device)) {
-                const size_t first = (region->first_bytes(n) + 15) & ~(size_t)15, bytes = first + region->second_bytes(n);
-                VRC_TRY(grow(g, g->region_in_bytes, bytes, {{g->d_region_in, bytes}}));
-                HIP_TRY(h, hipMemcpyAsync(g->d_region_in, positions, region->first_bytes(n), hipMemcpyDefault, g->stream));
-                HIP_TRY(h, hipMemcpyAsync(static_cast<char *>(g->d_region_in) + first, materials, region->second_bytes(n), hipMemcpyDefault, g->stream));
-                d_pos = static_cast<const int32_t *>(g->d_region_in); d_second = static_cast<const char *>(g->d_region_in) + first;
-            } else if (!on_device || g->device != h->device) {        // staged: the host's arrays, or rank 0's for a rank on another GPU
-                VRC_TRY(grow(g, g->edit_in_capacity, n, {{g->d_edit_in, sizeof(int32_t) * 4 * (size_t)n}}));
-                HIP_TRY(h, hipMemcpyAsync(g->d_edit_in, positions, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDefault, g->stream));
-                HIP_TRY(h, hipMemcpyAsync(g->d_edit_in + 3 * n, materials, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, g->stream));
-                d_pos = g->d_edit_in; d_mat = g->d_edit_in + 3 * n;
-            } else {
-                VRC_TRY(wait_for_null_stream(g));
-            }
-            const int rc = region ? region_stage(g, *region, d_pos, d_second, n, *stages.back()) : edit_stage(g, d_pos, d_mat, n, *stages.back());
-            if (rc != VRC_OK) return g == h ? rc : fail(h, rc, "rank %zu: %s", r, g->error.c_str());
-        }
-        const EditStage &s0 = *stages[0];
-        out.skipped = s0.skipped; out.voxels_changed = s0.changed; out.seconds = s0.seconds;
-        if (svo && s0.commit) {
-            for (auto &st : stages)
-                if (st->ran && st->commit) edit_commit(*st);
-            for (vrc_caster *g : group) VRC_TRY(set_setting(g, "octree_root_index", "OCTREE_ROOT_INDEX", (int64_t)s0.root));
-            out.bricks_touched = s0.bricks; out.descriptors_added = s0.added;
-        }
-        HIP_TRY(h, hipSetDevice(h->device));
-    }
-    if (svo) {
-        out.n_descriptors = h->tree->n_desc;
-        out.root_index = (uint64_t)setting_or(h, "octree_root_index", 0);
-    }
-    if (info) {
-        const uint32_t bytes = std::min<uint32_t>(info->struct_size, (uint32_t)sizeof(out));
-        out.struct_size = bytes;
-        memcpy(info, &out, bytes);
-    }
-    return VRC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vrc_set_voxels(vrc_caster *h, const int32_t *positions, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    VRC_TRY(edit_check(h, positions, materials, n, flags, "set_voxels"));
-    for (int64_t i = 0; i < n; i++)
-        if (materials[i] < -128 || materials[i] > 127)
-            return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels: materials[%lld] = %d is outside [-128, 127]", (long long)i, (int)materials[i]);
-    return edit_run(h, positions, materials, n, false, info, "set_voxels");
-}
-
-int vrc_set_voxels_device(vrc_caster *h, const void *d_positions, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    VRC_TRY(edit_check(h, d_positions, d_materials, n, flags, "set_voxels_device"));
-    if (n > 0) {
-        if (((uintptr_t)d_positions & 3u) || ((uintptr_t)d_materials & 3u))
-            return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels_device: positions and materials must be 4-byte aligned");
-        DeviceRestore restore;
-        HIP_TRY(h, hipSetDevice(h->device));
-        if (!query_pointer_ok(h, d_positions) || !query_pointer_ok(h, d_materials))
-            return fail(h, VRC_ERR_INVALID_ARGUMENT, "set_voxels_device: positions and materials must be memory the GPU of the handle (device %d) can read", h->device);
-    }
-    return edit_run(h, static_cast<const int32_t *>(d_positions), static_cast<const int32_t *>(d_materials), n, true, info, "set_voxels_device");
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// region edits (vrc_fill_boxes / vrc_write_regions and their _device variants, region_write.hip)
-// ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// the argument checks of the four calls, then the edit's readiness checks; nothing is launched when one fails
-int write_check(vrc_caster *h, const void *first, const void *second, int64_t n, uint32_t flags, bool paste, const char *what) {
-    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
-    const uint32_t known = VRC_WRITE_WHERE_EMPTY | VRC_WRITE_WHERE_SOLID | (paste ? VRC_WRITE_SKIP_ZERO : 0u);
-    if (flags & ~known) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~known));
-    if ((flags & VRC_WRITE_WHERE_EMPTY) && (flags & VRC_WRITE_WHERE_SOLID))
-        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: WHERE_EMPTY and WHERE_SOLID exclude each other", what);
-    if (n > 0 && (!first || !second)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null %s", what, paste ? "corners or data" : "boxes or materials");
-    if (n > INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 operations in one batch", what);
-    VRC_TRY(query_check(h, first, n, 0, 0, second, what));
-    if (setting_or(h, "using_octree", 0) == 0) return group_alone_holds_trees(h, what);
-    // the array branch: with dy > dz the frame's index x + dx * (y + dz * z) is not one-to-one over map_dim
-    if (h->map_dim[1] > h->map_dim[2]) return fail(h, VRC_ERR_LIMIT, "%s: a map with dy = %d > dz = %d has voxels that share a byte", what, h->map_dim[1], h->map_dim[2]);
-    for (const vrc_caster *g : h->peers)
-        if (g->map_dim[1] > g->map_dim[2]) return fail(h, VRC_ERR_LIMIT, "%s: a rank's map has dy > dz", what);
-    return VRC_OK;
-}
-
-// size and n_bytes of the pastes, as region_check's: *volume = V
-int write_size_check(vrc_caster *h, int64_t n, const int32_t size[3], size_t n_bytes, uint64_t *volume, const char *what) {
-    if (!size) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null size", what);
-    for (int a = 0; a < 3; a++)
-        if (size[a] < 1) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: size[%d] = %d < 1", what, a, (int)size[a]);
-    size_t bytes = (size_t)size[0];
-    for (uint64_t f : {(uint64_t)size[1], (uint64_t)size[2]}) {
-        if (bytes > SIZE_MAX / f) return fail(h, VRC_ERR_LIMIT, "%s: size[0] * size[1] * size[2] bytes overflows size_t", what);
-        bytes *= (size_t)f;
-    }
-    *volume = bytes;
-    if (n > 0 && bytes > SIZE_MAX / (uint64_t)n) return fail(h, VRC_ERR_LIMIT, "%s: n * size[0] * size[1] * size[2] bytes overflows size_t", what);
-    bytes *= (size_t)std::max<int64_t>(n, 0);
-    if (bytes > (size_t)INT64_MAX) return fail(h, VRC_ERR_LIMIT, "%s: more than 2^63 bytes", what);
-    if (n >= 0 && n_bytes < bytes) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: data holds %zu bytes, the regions need %zu", what, n_bytes, bytes);
-    return VRC_OK;
-}
-
-int write_device_pointers(vrc_caster *h, const void *d_first, const void *d_second, bool second_aligned, const char *what) {
-    if (((uintptr_t)d_first & 3u) || (second_aligned && ((uintptr_t)d_second & 3u)))
-        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned", what, second_aligned ? "boxes and materials" : "the corners");
-    DeviceRestore restore;
-    HIP_TRY(h, hipSetDevice(h->device));
-    if (!query_pointer_ok(h, d_first) || !query_pointer_ok(h, d_second))
-        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: the arrays must be memory the GPU of the handle (device %d) can read", what, h->device);
-    return VRC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vrc_fill_boxes(vrc_caster *h, const int32_t *boxes, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    VRC_TRY(write_check(h, boxes, materials, n, flags, false, "fill_boxes"));
-    for (int64_t i = 0; i < n; i++) {
-        if (materials[i] < -128 || materials[i] > 127)
-            return fail(h, VRC_ERR_INVALID_ARGUMENT, "fill_boxes: materials[%lld] = %d is outside [-128, 127]", (long long)i, (int)materials[i]);
-        for (int a = 0; a < 3; a++)
-            if (boxes[6 * i + 3 + a] < 1)
-                return fail(h, VRC_ERR_INVALID_ARGUMENT, "fill_boxes: box %lld has size[%d] = %d < 1", (long long)i, a, (int)boxes[6 * i + 3 + a]);
-    }
-    const RegionBatch b{0, flags, {0, 0, 0}, 0, "fill_boxes"};
-    return edit_run(h, boxes, materials, n, false, info, b.what, &b);
-}
-
-int vrc_fill_boxes_device(vrc_caster *h, const void *d_boxes, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    VRC_TRY(write_check(h, d_boxes, d_materials, n, flags, false, "fill_boxes_device"));
-    if (n > 0) VRC_TRY(write_device_pointers(h, d_boxes, d_materials, true, "fill_boxes_device"));
-    const RegionBatch b{0, flags, {0, 0, 0}, 0, "fill_boxes_device"};
-    return edit_run(h, d_boxes, d_materials, n, true, info, b.what, &b);
-}
-
-int vrc_write_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], const int8_t *data, size_t n_bytes, uint32_t flags, vrc_edit_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    uint64_t volume = 0;
-    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "write_regions: n = %lld < 0", (long long)n);
-    VRC_TRY(write_size_check(h, n, size, n_bytes, &volume, "write_regions"));
-    VRC_TRY(write_check(h, lo, data, n, flags, true, "write_regions"));
-    const RegionBatch b{1, flags, {size[0], size[1], size[2]}, volume, "write_regions"};
-    return edit_run(h, lo, data, n, false, info, b.what, &b);
-}
-
-int vrc_write_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], const void *d_data, size_t n_bytes, uint32_t flags, vrc_edit_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    uint64_t volume = 0;
-    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "write_regions_device: n = %lld < 0", (long long)n);
-    VRC_TRY(write_size_check(h, n, size, n_bytes, &volume, "write_regions_device"));
-    VRC_TRY(write_check(h, d_lo, d_data, n, flags, true, "write_regions_device"));
-    if (n > 0) VRC_TRY(write_device_pointers(h, d_lo, d_data, false, "write_regions_device"));
-    const RegionBatch b{1, flags, {size[0], size[1], size[2]}, volume, "write_regions_device"};
-    return edit_run(h, d_lo, d_data, n, true, info, b.what, &b);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// octree compaction (vrc_compact_octree, octree_compact.hip)
-// ---------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-// device memory of one call: the lists, scans and sizes of every level.  Freed when the call ends, so none of it outlives the tree.
-struct CompactScratch {
-    int device = 0;
-    std::vector<void *> held;
-    explicit CompactScratch(int dev) : device(dev) {}
-    CompactScratch(const CompactScratch &) = delete;
-    CompactScratch &operator=(const CompactScratch &) = delete;
-    template <class T>
-    hipError_t get(T *&p, uint64_t n) {
-        void *v = nullptr;
-        const hipError_t e = hipMalloc(&v, (size_t)std::max<uint64_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) { held.push_back(v); p = static_cast<T *>(v); }
-        return e;
-    }
-    ~CompactScratch() {
-        DeviceRestore restore;
-        (void)hipSetDevice(device);
-        for (void *v : held) (void)hipFree(v);
-        (void)hipGetLastError();
-    }
-};
-
-// What one handle's compaction has prepared: the staged arrays edit_commit installs, and the counts of vrc_compact_info.
-struct CompactStage : EditStage {
-    uint64_t before = 0, far = 0, attach_before = 0;
-};
-
-// One handle's compaction up to the commit (current device: g->device).  dry: sweeps 1 and 2 and the used attachment slots only.
-int compact_stage(vrc_caster *g, bool dry, CompactStage &st) {
-    st.h = g; st.ran = true;
-    vrc_tree *t = g->tree.get();
-    std::unique_lock<std::mutex> lock(t->guard);
-    HIP_TRY(g, hipStreamSynchronize(g->stream));                      // a frame in flight finishes first
-    vrc::CompactParams q;
-    memset(&q, 0, sizeof(q));
-    bind_scene(g, t, q.scene);
-    q.scene.coarse = nullptr; q.scene.coarse_log2 = 0;
-    const int n = q.scene.log2_dim;
-    const bool have = q.scene.attach_lookup != nullptr;
-    q.n_old = t->n_desc;
-    q.n_attach_old = have ? std::max<uint64_t>(t->n_attach, 1) : 0;
-    q.reach = (uint64_t)setting_or(g, "compact_near_reach", vrc::kCompactReachMax);
-    st.before = q.n_old; st.attach_before = q.n_attach_old;
-    CompactScratch mem(g->device);
-    EditTimer timer;
-    HIP_TRY(g, timer.init());
-    // the kernels run in segments, each ended by the read-back that sizes the next one
-    auto begin = [&]() { return hipEventRecord(timer.a, g->stream); };
-    auto end = [&]() {
-        hipError_t e = hipEventRecord(timer.b, g->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-        if (e == hipSuccess) timer.add(&st.seconds);
-        return e;
-    };
-    auto scan = [&](const uint64_t *in, uint64_t *out, uint64_t count) {
-        size_t bytes = 0;
-        char *temp = nullptr;
-        hipError_t e = vrc::compact_scan(nullptr, &bytes, in, out, count, g->stream);
-        if (e == hipSuccess) e = mem.get(temp, bytes);
-        if (e == hipSuccess) e = vrc::compact_scan(temp, &bytes, in, out, count, g->stream);
-        return e;
-    };
-    HIP_TRY(g, mem.get(q.counters, vrc::kCompactCounters));
-    HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(unsigned long long) * vrc::kCompactCounters, g->stream));
-
-    // sweep 1, top-down: the pointer-holding descriptors of every level above the bottom
-    uint64_t root_word = 0;
-    HIP_TRY(g, hipMemcpy(&root_word, t->d_desc + q.scene.root_index, sizeof(root_word), hipMemcpyDeviceToHost));
-    std::vector<vrc::CompactLevel> levels;
-    uint64_t count = (n > 1 && ((root_word >> 16) & 0xffULL)) ? 1 : 0;
-    uint64_t *list = nullptr;
-    if (count) {
-        HIP_TRY(g, mem.get(list, 1));
-        HIP_TRY(g, hipMemcpy(list, &q.scene.root_index, sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    for (int l = 0; l <= n - 2 && count > 0; l++) {
-        vrc::CompactLevel L;
-        memset(&L, 0, sizeof(L));
-        L.list = list; L.count = (int64_t)count; L.level = l; L.children_bottom = l == n - 2 ? 1 : 0;
-        uint64_t *sums = nullptr, *base = nullptr;
-        HIP_TRY(g, mem.get(L.pmask, count)); HIP_TRY(g, mem.get(L.farmask, count)); HIP_TRY(g, mem.get(L.size, count));
-        HIP_TRY(g, mem.get(L.cnt, count + 1)); HIP_TRY(g, mem.get(sums, count + 1)); HIP_TRY(g, mem.get(base, count));
-        L.scan = sums; L.base = base;
-        HIP_TRY(g, begin());
-        if (!levels.empty()) HIP_TRY(g, vrc::launch_compact_level(q, levels.back(), 1, g->stream));    // (this level's list)
-        HIP_TRY(g, vrc::launch_compact_level(q, L, 0, g->stream));
-        HIP_TRY(g, scan(L.cnt, sums, count + 1));
-        HIP_TRY(g, end());
-        uint64_t next = 0;
-        HIP_TRY(g, hipMemcpy(&next, sums + count, sizeof(next), hipMemcpyDeviceToHost));
-        if (next > q.n_old) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: level %d holds more descriptors than the array: not a tree", l + 1);
-        list = nullptr;
-        if (next) HIP_TRY(g, mem.get(list, next));
-        L.next_list = list;
-        levels.push_back(L);
-        count = next;
-    }
-    if (count) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: the bottom level holds pointers: not a tree");
-    for (size_t l = 0; l + 1 < levels.size(); l++) { levels[l].size_below = levels[l + 1].size; levels[l].base_below = const_cast<uint64_t *>(levels[l + 1].base); }
-
-    // sweep 2, bottom-up: the subtree sizes and the far children
-    uint64_t below_root = 0;
-    if (!levels.empty()) {
-        HIP_TRY(g, begin());
-        for (size_t l = levels.size(); l-- > 0;) HIP_TRY(g, vrc::launch_compact_level(q, levels[l], 2, g->stream));
-        HIP_TRY(g, end());
-        HIP_TRY(g, hipMemcpy(&below_root, levels[0].size, sizeof(below_root), hipMemcpyDeviceToHost));
-    }
-    unsigned long long c[vrc::kCompactCounters];
-    HIP_TRY(g, hipMemcpy(c, q.counters, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[vrc::kCompactBad]) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: the tree points outside its array (%llu indices)", c[vrc::kCompactBad]);
-    st.n_desc = 1 + below_root; st.far = c[vrc::kCompactFar]; st.root = 0;
-    if (st.n_desc >= (1ULL << 47)) return fail(g, VRC_ERR_LIMIT, "compact_octree: more than 2^47 descriptors");
-
-    // the new arrays, beside the old ones until the commit
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-    auto staged = [&](auto *&p, uint64_t &cap, uint64_t need, size_t elem) -> int {
-        cap = need + edit_reserve_for(g, need, elem, free_b);
-        const hipError_t e = hipMalloc((void **)&p, cap * elem);
-        if (e == hipSuccess) return VRC_OK;
-        (void)hipGetLastError();
-        p = nullptr;
-        return fail(g, e == hipErrorOutOfMemory ? VRC_ERR_OUT_OF_MEMORY : VRC_ERR_DEVICE, "compact_octree: allocating the new arrays (%llu words) beside the old ones failed: %s",
-                    (unsigned long long)need, hipGetErrorString(e));
-    };
-    if (!dry) {
-        VRC_TRY(staged(st.desc, st.cap_desc, st.n_desc, sizeof(uint64_t)));
-        q.out = st.desc; q.n_out = st.n_desc;
-        if (have) {
-            VRC_TRY(staged(st.lookup, st.cap_lookup, st.n_desc, sizeof(uint32_t)));
-            HIP_TRY(g, hipMemsetAsync(st.lookup, 0, st.n_desc * sizeof(uint32_t), g->stream));
-            q.out_lookup = st.lookup;
-        }
-        if (!levels.empty()) {
-            const uint64_t one = 1;
-            HIP_TRY(g, hipMemcpy(const_cast<uint64_t *>(levels[0].base), &one, sizeof(one), hipMemcpyHostToDevice));
-        }
-    }
-    uint64_t *remap = nullptr;
-    if (have) {
-        HIP_TRY(g, mem.get(q.used, q.n_attach_old + 1));
-        HIP_TRY(g, mem.get(remap, q.n_attach_old + 1));
-        HIP_TRY(g, hipMemsetAsync(q.used, 0, (q.n_attach_old + 1) * sizeof(uint64_t), g->stream));
-    }
-
-    // sweep 3, top-down: the blocks, the far slots, the lookup words, the used attachment slots (a dry run: only those, which
-    // the parents of the bottom level raise)
-    HIP_TRY(g, begin());
-    if (!dry || have) HIP_TRY(g, vrc::launch_compact_root(q, g->stream));
-    for (const vrc::CompactLevel &L : levels)
-        if (!dry || (have && L.children_bottom)) HIP_TRY(g, vrc::launch_compact_level(q, L, 3, g->stream));
-    if (have) HIP_TRY(g, scan(q.used, remap, q.n_attach_old + 1));
-    HIP_TRY(g, end());
-    if (have) {
-        uint64_t kept = 0;
-        HIP_TRY(g, hipMemcpy(&kept, remap + q.n_attach_old, sizeof(kept), hipMemcpyDeviceToHost));
-        st.n_attach = std::max<uint64_t>(kept, 1);                   // (a tree with materials keeps a slot: slot 0 = eight 5s, as the edit creates it)
-        if (!dry) {
-            VRC_TRY(staged(st.attach, st.cap_attach, st.n_attach, sizeof(uint64_t)));
-            HIP_TRY(g, begin());
-            if (!kept) HIP_TRY(g, hipMemsetAsync(st.attach, 0x05, sizeof(uint64_t), g->stream));
-            HIP_TRY(g, vrc::launch_compact_materials(q, remap, st.n_desc, st.attach, kept, g->stream));
-            HIP_TRY(g, end());
-        }
-    }
-    HIP_TRY(g, hipMemcpy(c, q.counters, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[vrc::kCompactBad]) return fail(g, VRC_ERR_INVALID_ARGUMENT, "compact_octree: the tree points outside its array (%llu indices)", c[vrc::kCompactBad]);
-    st.commit = !dry;
-    return VRC_OK;
-}
-
-int compact_run(vrc_caster *h, bool dry, vrc_compact_info *info) {
-    vrc_compact_info out;
-    memset(&out, 0, sizeof(out));
-    DeviceRestore restore;
-    if (setting_or(h, "using_octree", 0) == 0) {
-        std::vector<vrc_caster *> group{h};
-        group.insert(group.end(), h->peers.begin(), h->peers.end());
-        std::vector<std::unique_ptr<CompactStage>> stages;
-        // every rank stages its new arrays (a rank that shares an earlier rank's tree has nothing to do), then all of them commit
-        for (size_t r = 0; r < group.size(); r++) {
-            vrc_caster *g = group[r];
-            stages.emplace_back(new CompactStage());
-            bool shared = false;
-            for (size_t k = 0; k < r; k++) shared = shared || group[k]->tree.get() == g->tree.get();
-            if (shared) continue;
-            HIP_TRY(h, hipSetDevice(g->device));
-            const int rc = compact_stage(g, dry, *stages.back());
-            if (rc != VRC_OK) return g == h ? rc : fail(h, rc, "rank %zu: %s", r, g->error.c_str());
-        }
-        const CompactStage &s0 = *stages[0];
-        if (!dry) {
-            for (auto &st : stages)
-                if (st->ran && st->commit) edit_commit(*st);
-            for (vrc_caster *g : group) VRC_TRY(set_setting(g, "octree_root_index", "OCTREE_ROOT_INDEX", 0));
-#ifdef VRC_INDEX_AUDIT
-            // the tables still hold the old tree's extents, and the new arrays are SHORTER: what runs next is held against the new ones
-            for (vrc_caster *g : group) {
-                HIP_TRY(h, hipSetDevice(g->device));
-                std::lock_guard<std::mutex> lock(g->tree->guard);
-                AuditExtents x;
-                audit_tree(x, g->tree.get());
-                VRC_AUDIT_PUBLISH(h, x);
-            }
-#endif
-        }
-        HIP_TRY(h, hipSetDevice(h->device));
-        out.descriptors_before = s0.before; out.n_descriptors = s0.n_desc; out.root_index = 0;
-        out.live_descriptors = s0.n_desc - s0.far; out.far_slots = s0.far;
-        out.attachments_before = s0.attach_before; out.n_attachments = s0.n_attach;
-        out.seconds = s0.seconds;
-    }
-    if (info) {
-        const uint32_t bytes = std::min<uint32_t>(info->struct_size, (uint32_t)sizeof(out));
-        out.struct_size = bytes;
-        memcpy(info, &out, bytes);
-    }
-    return VRC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vrc_compact_octree(vrc_caster *h, uint32_t flags, vrc_compact_info *info) {
-    if (!h) return VRC_ERR_INVALID_ARGUMENT;
-    const char *what = "compact_octree";
-    if (flags & ~(uint32_t)VRC_COMPACT_DRY_RUN) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~(uint32_t)VRC_COMPACT_DRY_RUN));
-    if (info && info->struct_size < sizeof(uint32_t)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: info->struct_size is not set", what);
-    const int64_t reach = setting_or(h, "compact_near_reach", vrc::kCompactReachMax);
-    if (reach < vrc::kCompactReachMin || reach > vrc::kCompactReachMax)
-        return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: compact_near_reach = %lld is outside [%lld, %lld]", what, (long long)reach, (long long)vrc::kCompactReachMin, (long long)vrc::kCompactReachMax);
-    VRC_TRY(query_check(h, nullptr, 0, 0, 0, nullptr, what));
-    if (setting_or(h, "using_octree", 0) == 0) VRC_TRY(group_alone_holds_trees(h, what));
-    return compact_run(h, (flags & VRC_COMPACT_DRY_RUN) != 0, info);
 }
 
 }  // extern "C"
