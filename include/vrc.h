@@ -494,6 +494,53 @@ int vrc_get_voxels_device(vrc_caster *h, const void *d_positions, int64_t n, voi
 int vrc_read_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], int8_t *out, size_t n_bytes);
 int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], void *d_out, size_t n_bytes);
 
+/* ---- exposed faces -------------------------------------------------------- */
+
+/* Where is the scene's surface?  The exposed voxel faces of n regions -- for a mesher, a physics engine's collision geometry, a
+ * minimap, a navigation builder, an instance buffer -- without moving the regions' voxels to the host: a terrain's surface is a
+ * thin shell, and after vrc_set_voxels / vrc_fill_boxes only the touched chunks are extracted again.  Read-only.
+ *
+ * The material of voxel (x, y, z) is vrc_get_voxels', in either branch (the branch follows using_octree); outside the scene it
+ * is 0.  A voxel is SOLID when its material is non-zero; with VRC_FACES_STOPPING_ONLY only when its material is 5 or 6 -- every
+ * other value then counts as empty, as an owner and as a neighbour: the mesh of what the renderer draws.  Directions d = 0 .. 5
+ * stand for -x, +x, -y, +y, -z, +z.  Face (v, d) exists when v is solid, v lies in its region and in the scene, and the
+ * neighbour v + e_d is not solid.  The neighbour is read from the SCENE, not from the region: no face appears on a chunk seam
+ * inside solid ground, and regions that tile the map yield disjoint face sets whose union is the whole map's set.  A neighbour
+ * outside the scene is empty, so the map's own sides and bottom are faces; VRC_FACES_NO_MAP_EDGE drops exactly the faces whose
+ * neighbour lies outside the scene.
+ *
+ * lo and size are vrc_read_regions': n regions [lo_i, lo_i + size) of one common size, lo int32[3 n], any int32; a region may
+ * lie partly or wholly outside the scene, and that part owns no faces.  counts int64[n] receives the faces of every region,
+ * always exact.  faces int32[4 capacity] receives the packed list: an entry is x, y, z, code with code = d | (material & 0xff)
+ * << 8, and region i's entries start at the sum of counts[0 .. i).  Inside a region the faces are sorted by the brick coordinate
+ * (v >> 3) - (lo_i >> 3), z-major (brick z, then brick y, then brick x), then by v.z, v.y, v.x, then by d.  Entries at or beyond
+ * `capacity` are not written and memory past the written entries is not touched.  faces may be NULL iff capacity == 0: a
+ * count-only call.  info may be NULL; set info->struct_size = sizeof(vrc_faces_info) before the call.
+ *
+ * Host rules as vrc_box_intersection: synchronous on the handle's stream (a frame in flight finishes first); the image, hit
+ * records, counters, timing and vrc_last_kernel are untouched; the coarse table is used when it is built and never built here,
+ * with the same results without it; rank 0's GPU for a group, the caller's device restored; staging and scratch grow on demand
+ * and are freed by vrc_release_map / _octree / _viewport and vrc_destroy.  One host wait in the middle: the total sizes the
+ * list pass, which runs only when capacity > 0.  The _device variant takes memory the handle's GPU can read and write and waits
+ * for the null stream first; d_lo and d_faces must be 4-byte aligned, d_counts 8-byte aligned.
+ * Errors, with nothing launched: VRC_ERR_INVALID_ARGUMENT for a null handle or a null required pointer, n < 0, a size
+ * component < 1, capacity < 0, unknown flag bits, misalignment or an info whose struct_size is below 4; VRC_ERR_LIMIT when
+ * n times the bricks a region can touch ((size + 6) / 8 + 1 per axis) exceeds 2^31 - 1 or capacity * 16 overflows size_t;
+ * VRC_ERR_NOT_READY as for ray queries.  n = 0 succeeds.                                                                      */
+#define VRC_FACES_NO_MAP_EDGE   1u
+#define VRC_FACES_STOPPING_ONLY 2u
+typedef struct vrc_faces_info {         /* size-versioned like vrc_edit_info */
+    uint32_t struct_size;               /* in: sizeof the caller's struct; out: bytes written */
+    uint32_t truncated;                 /* 1 when faces_total > capacity */
+    int64_t  faces_total;               /* the sum of counts */
+    int64_t  faces_written;             /* min(faces_total, capacity) */
+    double   seconds;                   /* device time of the call's kernels */
+} vrc_faces_info;
+int vrc_extract_faces(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags,
+                      int64_t *counts, int32_t *faces, vrc_faces_info *info);
+int vrc_extract_faces_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags,
+                             void *d_counts, void *d_faces, vrc_faces_info *info);
+
 /* ---- voxel edits ---------------------------------------------------------- */
 
 /* Change the scene.  Map::setVoxel / ArrayMap::setVoxel (include/map/Map.h:42, ArrayMap.h:17) as a batch against the scene the

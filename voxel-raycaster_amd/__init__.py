@@ -99,6 +99,14 @@ class EditInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n not in ("struct_size", "reserved_")}
 
 
+class FacesInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("truncated", C.c_uint32), ("faces_total", C.c_int64), ("faces_written", C.c_int64),
+                ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "struct_size"}
+
+
 class CompactInfo(C.Structure):
     _fields_ = ([("struct_size", C.c_uint32), ("reserved_", C.c_uint32)]
                 + [(n, C.c_uint64) for n in ("descriptors_before", "n_descriptors", "root_index", "live_descriptors", "far_slots",
@@ -211,6 +219,8 @@ SIGNATURES = {
     "vrc_get_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
     "vrc_read_regions": (C.c_int, [_H, _i32p, C.c_int64, _i32p, C.POINTER(C.c_int8), C.c_size_t]),
     "vrc_read_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t]),
+    "vrc_extract_faces": (C.c_int, [_H, _i32p, C.c_int64, _i32p, C.c_int64, C.c_uint32, C.POINTER(C.c_int64), _i32p, C.POINTER(FacesInfo)]),
+    "vrc_extract_faces_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(FacesInfo)]),
     "vrc_set_voxels": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_set_voxels_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_fill_boxes": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
@@ -231,6 +241,8 @@ RAY_HIT, RAY_LEFT_MAP, RAY_STEP_CAP, RAY_REJECTED = 1, 2, 4, 8
 # box queries (vrc_box_intersection): the flag, and the bits of record field 0
 BOX_STOPPING_ONLY = 1
 BOX_ANY, BOX_TRUNCATED, BOX_CLIPPED, BOX_REJECTED = 1, 2, 4, 8
+# exposed faces (vrc_extract_faces): the flags
+FACES_NO_MAP_EDGE, FACES_STOPPING_ONLY = 1, 2
 # swept-box queries (vrc_sweep_boxes): the flag, and the bits of record field 0
 SWEEP_STOPPING_ONLY = 1
 SWEEP_HIT, SWEEP_START_SOLID, SWEEP_CLIPPED, SWEEP_REJECTED, SWEEP_EVENT_CAP, SWEEP_LEFT_MAP = 1, 2, 4, 8, 16, 32
@@ -929,6 +941,58 @@ class CLCaster:
         if sz.shape != (3,):
             raise VrcError(f"read_regions_device: size must be three integers, got {size}")
         return self._ok(lib.vrc_read_regions_device(self._h, C.c_void_p(lo_ptr), int(n), _ptr(sz, _i32p), C.c_void_p(out_ptr), int(n_bytes)))
+
+    # -- exposed faces (vrc_extract_faces, include/vrc.h)
+    @staticmethod
+    def _faces_args(what, size, no_map_edge, stopping_only):
+        sz = np.ascontiguousarray(size, dtype=np.int32)
+        if sz.shape != (3,):
+            raise VrcError(f"{what}: size must be three integers, got {size}")
+        info = FacesInfo()
+        info.struct_size = C.sizeof(FacesInfo)
+        return sz, (FACES_NO_MAP_EDGE if no_map_edge else 0) | (FACES_STOPPING_ONLY if stopping_only else 0), info
+
+    def extract_faces(self, lo: np.ndarray, size, capacity: Optional[int] = None, no_map_edge: bool = False, stopping_only: bool = False):
+        """The exposed voxel faces of the regions [lo[i], lo[i] + size): lo (n, 3) int32, size = (sx, sy, sz) common to all ->
+        (counts (n,) int64, faces (k, 4) int32 = x, y, z, d | (material & 0xff) << 8 with d = 0 .. 5 for -x, +x, -y, +y, -z, +z,
+        info dict: truncated, faces_total, faces_written, seconds).  Region i's faces start at counts[:i].sum(), in the order
+        include/vrc.h states.  capacity = None makes a count-only call and then a call of exactly that size (k = faces_total);
+        a given capacity makes one call and k = min(faces_total, capacity).  no_map_edge drops the faces on the scene's own
+        sides; stopping_only counts only the materials 5 and 6 as solid.  Raises on failure."""
+        c = np.ascontiguousarray(lo, dtype=np.int32)
+        if c.ndim != 2 or c.shape[1] != 3:
+            raise VrcError(f"extract_faces: lo must have shape (n, 3), got {c.shape}")
+        sz, flags, info = self._faces_args("extract_faces", size, no_map_edge, stopping_only)
+        n = c.shape[0]
+        counts = np.zeros(n, dtype=np.int64)
+
+        def call(cap, faces):
+            if not self._ok(lib.vrc_extract_faces(self._h, _ptr(c, _i32p), n, _ptr(sz, _i32p), cap, flags, _ptr(counts, C.POINTER(C.c_int64)),
+                                                  _ptr(faces, _i32p) if cap > 0 else None, C.byref(info))):
+                raise VrcError(self.last_error())
+
+        if capacity is None:
+            call(0, None)
+            capacity = int(info.faces_total)
+            if capacity == 0:
+                return counts, np.empty((0, 4), dtype=np.int32), info.as_dict()
+        capacity = int(capacity)
+        if capacity < 0:
+            raise VrcError(f"extract_faces: capacity = {capacity} < 0")
+        faces = np.empty((capacity, 4), dtype=np.int32)
+        call(capacity, faces)
+        return counts, faces[:int(info.faces_written)], info.as_dict()
+
+    def extract_faces_device(self, lo_ptr: int, n: int, size, counts_ptr: int, faces_ptr: int = 0, capacity: int = 0,
+                             no_map_edge: bool = False, stopping_only: bool = False) -> dict:
+        """extract_faces on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 3 int32 corners, n int64 counts,
+        capacity x 4 int32 faces; capacity = 0 only counts).  Returns the info dict; entries past faces_written are not touched.
+        Raises on failure."""
+        sz, flags, info = self._faces_args("extract_faces_device", size, no_map_edge, stopping_only)
+        if not self._ok(lib.vrc_extract_faces_device(self._h, C.c_void_p(lo_ptr), int(n), _ptr(sz, _i32p), int(capacity), flags,
+                                                     C.c_void_p(counts_ptr), C.c_void_p(faces_ptr or None), C.byref(info))):
+            raise VrcError(self.last_error())
+        return info.as_dict()
 
     # -- voxel edits (vrc_set_voxels, include/vrc.h)
     def set_voxels(self, positions: np.ndarray, materials) -> dict:

@@ -169,6 +169,27 @@ public:
     bool read_regions_device(const void *d_lo, int64_t n, const int32_t size[3], void *d_materials, size_t n_bytes) {
         return ok(vrc_read_regions_device(h_, d_lo, n, size, d_materials, n_bytes));
     }
+    // extension: the exposed voxel faces of such regions (vrc_extract_faces): counts = one int64 per region, faces = 4 int32 each
+    // (x, y, z, d | material << 8), packed in region order -- a count-only call, then a call of exactly that size
+    bool extract_faces(const std::vector<int32_t> &lo, const int32_t size[3], std::vector<int64_t> &counts, std::vector<int32_t> &faces,
+                       uint32_t flags = 0u, vrc_faces_info *info = nullptr) {
+        const int64_t n = (int64_t)(lo.size() / 3);
+        counts.resize((size_t)n);
+        vrc_faces_info first;
+        first.struct_size = (uint32_t)sizeof(first);
+        faces.clear();
+        if (!ok(vrc_extract_faces(h_, lo.data(), n, size, 0, flags, counts.data(), nullptr, &first))) return false;
+        if (info) *info = first;
+        if (first.faces_total == 0) return true;
+        faces.resize((size_t)4 * (size_t)first.faces_total);
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_extract_faces(h_, lo.data(), n, size, first.faces_total, flags, counts.data(), faces.data(), info));
+    }
+    bool extract_faces_device(const void *d_lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags, void *d_counts,
+                              void *d_faces, vrc_faces_info *info = nullptr) {
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_extract_faces_device(h_, d_lo, n, size, capacity, flags, d_counts, d_faces, info));
+    }
 
     // extension: Map::setVoxel (Map.h:42) as a batch against the resident scene (vrc_set_voxels): positions = 3 int32 each,
     // materials = one int32 each in [-128, 127], applied in index order; info (optional) receives what the edit did

@@ -16,6 +16,7 @@
 
 #include "box_query.h"
 #include "box_sweep.h"
+#include "face_extract.h"
 #include "raycast_query.h"
 #include "voxel_read.h"
 #include "vrc_host.hpp"
@@ -23,7 +24,7 @@
 #ifdef VRC_INDEX_AUDIT
 namespace vrc {
 #define VRC_AUDIT_DECLARE(name) hipError_t audit_publish_##name(const unsigned long long *extent_plus_1); hipError_t audit_collect_##name(audit::Stat *out, unsigned long long *extent_plus_1, int clear);
-VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit) VRC_AUDIT_DECLARE(compact) VRC_AUDIT_DECLARE(region)
+VRC_AUDIT_DECLARE(raycast) VRC_AUDIT_DECLARE(jump) VRC_AUDIT_DECLARE(boxes) VRC_AUDIT_DECLARE(query) VRC_AUDIT_DECLARE(boxq) VRC_AUDIT_DECLARE(sweep) VRC_AUDIT_DECLARE(read) VRC_AUDIT_DECLARE(edit) VRC_AUDIT_DECLARE(compact) VRC_AUDIT_DECLARE(region) VRC_AUDIT_DECLARE(faces)
 #undef VRC_AUDIT_DECLARE
 }  // namespace vrc
 #endif
@@ -46,12 +47,12 @@ void vrc_host::release_boxes(vrc_tree *t) {
 
 namespace {
 
-// vrc_cast_rays', vrc_box_intersection's, vrc_sweep_boxes', the voxel reads' and the voxel edits' staging and scratch buffers (the caller's device is left
+// vrc_cast_rays', vrc_box_intersection's, vrc_sweep_boxes', the voxel reads', the face extraction's and the voxel edits' staging and scratch buffers (the caller's device is left
 // as it was)
 void release_query_staging(vrc_caster *h) {
     if (!h->d_query_rays && !h->d_query_out && !h->d_box_in && !h->d_box_vox && !h->d_box_plan && !h->d_box_items && !h->d_box_temp &&
         !h->d_sweep_in && !h->d_sweep_rec && !h->d_read_in && !h->d_read_out && !h->d_edit_in && !h->d_edit_keys && !h->d_edit_counters &&
-        !h->d_edit_temp && !h->d_edit_levels && !h->d_edit_rec_masks && !h->d_region_in && !h->d_region_counts) return;
+        !h->d_edit_temp && !h->d_edit_levels && !h->d_edit_rec_masks && !h->d_region_in && !h->d_region_counts && !h->d_face_items) return;
     {
         DeviceRestore restore;
         (void)hipSetDevice(h->device);
@@ -64,6 +65,8 @@ void release_query_staging(vrc_caster *h) {
         h->sweep_io_capacity = 0; h->sweep_capacity = 0;
         release(h->d_read_in); release(h->d_read_out);
         h->read_in_capacity = 0; h->read_out_bytes = 0;
+        release(h->d_face_items);
+        h->face_item_capacity = 0;
         release(h->d_edit_in); release(h->d_edit_keys); release(h->d_edit_unique); release(h->d_edit_order); release(h->d_edit_counts);
         release(h->d_edit_counters); release(h->d_edit_temp); release(h->d_edit_levels); release(h->d_edit_rec_masks); release(h->d_edit_rec_child);
         h->edit_in_capacity = 0; h->edit_capacity = 0; h->edit_temp_bytes = 0; h->edit_level_capacity = 0; h->edit_rec_capacity = 0;
@@ -114,6 +117,7 @@ const AuditTu kAuditTus[] = {
     {vrc::audit_publish_boxq, vrc::audit_collect_boxq},       {vrc::audit_publish_sweep, vrc::audit_collect_sweep},
     {vrc::audit_publish_read, vrc::audit_collect_read},       {vrc::audit_publish_edit, vrc::audit_collect_edit},
     {vrc::audit_publish_compact, vrc::audit_collect_compact}, {vrc::audit_publish_region, vrc::audit_collect_region},
+    {vrc::audit_publish_faces, vrc::audit_collect_faces},
 };
 }  // namespace
 unsigned long long vrc_host::g_audit_shrink[vrc::audit::kArrayCount];
@@ -2117,6 +2121,162 @@ int vrc_read_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const in
     int rc = region_check(h, d_lo, n, size, d_out, n_bytes, &total, "read_regions_device");
     if (rc != VRC_OK || n == 0) return rc;
     return read_device(h, d_lo, n, size, d_out, "read_regions_device");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// exposed faces (vrc_extract_faces / vrc_extract_faces_device, face_extract.hip)
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// the argument checks of both calls, then the readiness checks of the ray queries; *items = n x the bricks a region can touch
+int faces_check(vrc_caster *h, const void *lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags, const void *counts,
+                const void *faces, const vrc_faces_info *info, int64_t *items, const char *what) {
+    if (n < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: n = %lld < 0", what, (long long)n);
+    VRC_TRY(size_check(h, size, what));
+    if (capacity < 0) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: capacity = %lld < 0", what, (long long)capacity);
+    const uint32_t known = VRC_FACES_NO_MAP_EDGE | VRC_FACES_STOPPING_ONLY;
+    if (flags & ~known) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", what, (unsigned)(flags & ~known));
+    if (n > 0 && (!lo || !counts)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null corners or counts", what);
+    if (n > 0 && capacity > 0 && !faces) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: null faces with capacity = %lld", what, (long long)capacity);
+    if (info && info->struct_size < sizeof(uint32_t)) return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: info->struct_size is not set", what);
+    if ((uint64_t)capacity > SIZE_MAX / 16u) return fail(h, VRC_ERR_LIMIT, "%s: capacity * 16 bytes overflows size_t", what);
+    // (axis by axis: a brick count is at most 2^28 + 1, so a product that passed the check times the next count fits 64 bits)
+    uint64_t per = 1;
+    for (int a = 0; a < 3; a++) {
+        per *= (uint64_t)(((int64_t)size[a] + 6) / 8 + 1);
+        if (per > (uint64_t)INT32_MAX) return fail(h, VRC_ERR_LIMIT, "%s: a region touches more than 2^31 - 1 bricks", what);
+    }
+    if (n > 0 && per > (uint64_t)INT32_MAX / (uint64_t)n) return fail(h, VRC_ERR_LIMIT, "%s: n * bricks per region exceeds 2^31 - 1", what);
+    *items = (int64_t)per * n;
+    return query_check(h, lo, n, 0, 0, counts, what);
+}
+
+// the device time between two events of the handle's stream, added up over the call's segments
+struct FaceTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~FaceTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipError_t init() { const hipError_t e = hipEventCreate(&a); return e == hipSuccess ? hipEventCreate(&b) : e; }
+    void add(double &seconds) {                               // (after the stream was waited for)
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, a, b) == hipSuccess) seconds += ms * 1e-3; else (void)hipGetLastError();
+    }
+};
+
+// One extraction on the handle's stream (current device: h->device), in two steps with a host wait after each.  The tree's guard
+// is held from begin to the end of emit, as box_enqueue holds it; the coarse table is used when it is built, never built here.
+struct FaceCall {
+    std::unique_lock<std::mutex> lock;
+    vrc::FaceParams q;
+    FaceTimer timer;
+    int64_t total = 0;
+    double seconds = 0.0;
+};
+
+// count, scan, per-region counts; the grand total comes back in one 8-byte copy.  d_counts == nullptr: the counts go to the
+// scratch behind the items' (the host call copies them out from c.q.counts)
+int faces_count(vrc_caster *h, FaceCall &c, const int32_t *d_lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags,
+                int64_t items, int64_t *d_counts) {
+    c.lock = std::unique_lock<std::mutex>(h->tree->guard);
+    vrc::FaceParams &q = c.q;
+    memset(&q, 0, sizeof(q));
+    q.lo = d_lo; q.n = n; q.flags = flags; q.capacity = capacity;
+    for (int a = 0; a < 3; a++) {
+        q.size[a] = size[a];
+        q.bricks[a] = ((int64_t)size[a] + 6) / 8 + 1;
+    }
+    VRC_TRY(grow(h, h->face_item_capacity, 2 * items + n, {{h->d_face_items, sizeof(int64_t) * (size_t)(2 * items + n)}}));
+    q.item_count = h->d_face_items; q.item_end = h->d_face_items + items;
+    q.counts = d_counts ? d_counts : h->d_face_items + 2 * items;
+    size_t need = 0;
+    HIP_TRY(h, vrc::box_scan(nullptr, &need, q.item_count, q.item_end, items, h->stream));
+    VRC_TRY(grow(h, h->box_temp_bytes, need, {{h->d_box_temp, need}}));
+    bind_scene(h, h->tree.get(), q.scene);
+    HIP_TRY(h, c.timer.init());
+    HIP_TRY(h, hipEventRecord(c.timer.a, h->stream));
+    HIP_TRY(h, vrc::launch_face_count(q, h->stream));
+    size_t bytes = h->box_temp_bytes;
+    HIP_TRY(h, vrc::box_scan(h->d_box_temp, &bytes, q.item_count, q.item_end, items, h->stream));
+    HIP_TRY(h, vrc::launch_face_regions(q, h->stream));
+    HIP_TRY(h, hipEventRecord(c.timer.b, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&c.total, q.item_end + items - 1, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    c.timer.add(c.seconds);
+    return VRC_OK;
+}
+
+// the list, into d_faces (capacity entries); waits for the stream
+int faces_emit(vrc_caster *h, FaceCall &c, int32_t *d_faces) {
+    if (c.q.capacity > 0 && c.total > 0) {
+        c.q.faces = d_faces;
+        HIP_TRY(h, hipEventRecord(c.timer.a, h->stream));
+        HIP_TRY(h, vrc::launch_face_emit(c.q, h->stream));
+        HIP_TRY(h, hipEventRecord(c.timer.b, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        c.timer.add(c.seconds);
+    }
+    return VRC_OK;
+}
+
+void faces_report(vrc_faces_info *info, int64_t total, int64_t capacity, double seconds) {
+    if (!info) return;
+    vrc_faces_info out;
+    memset(&out, 0, sizeof(out));
+    out.truncated = total > capacity ? 1u : 0u;
+    out.faces_total = total; out.faces_written = std::min(total, capacity); out.seconds = seconds;
+    write_info(info, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrc_extract_faces(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags,
+                      int64_t *counts, int32_t *faces, vrc_faces_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int64_t items = 0;
+    int rc = faces_check(h, lo, n, size, capacity, flags, counts, faces, info, &items, "extract_faces");
+    if (rc != VRC_OK) return rc;
+    if (n == 0) { faces_report(info, 0, capacity, 0.0); return VRC_OK; }
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    VRC_TRY(grow(h, h->read_in_capacity, n, {{h->d_read_in, sizeof(int32_t) * 3 * (size_t)n}}));
+    HIP_TRY(h, hipMemcpyAsync(h->d_read_in, lo, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    FaceCall c;
+    VRC_TRY(faces_count(h, c, h->d_read_in, n, size, capacity, flags, items, nullptr));
+    HIP_TRY(h, hipMemcpyAsync(counts, c.q.counts, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    // the list is staged at the size it has, not at the size the caller made room for; only the written entries go back
+    const size_t list_bytes = sizeof(int32_t) * 4 * (size_t)std::min(c.total, capacity);
+    if (list_bytes) VRC_TRY(grow(h, h->read_out_bytes, list_bytes, {{h->d_read_out, list_bytes}}));
+    c.q.capacity = std::min(c.total, capacity);
+    VRC_TRY(faces_emit(h, c, static_cast<int32_t *>(h->d_read_out)));
+    if (list_bytes) HIP_TRY(h, hipMemcpyAsync(faces, h->d_read_out, list_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    faces_report(info, c.total, capacity, c.seconds);
+    return VRC_OK;
+}
+
+int vrc_extract_faces_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], int64_t capacity, uint32_t flags,
+                             void *d_counts, void *d_faces, vrc_faces_info *info) {
+    if (!h) return VRC_ERR_INVALID_ARGUMENT;
+    int64_t items = 0;
+    int rc = faces_check(h, d_lo, n, size, capacity, flags, d_counts, d_faces, info, &items, "extract_faces_device");
+    if (rc != VRC_OK) return rc;
+    if (n == 0) { faces_report(info, 0, capacity, 0.0); return VRC_OK; }
+    const bool list = capacity > 0;
+    if (((uintptr_t)d_lo & 3u) || ((uintptr_t)d_counts & 7u) || (list && ((uintptr_t)d_faces & 3u)))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "extract_faces_device: the corners and faces must be 4-byte aligned, counts 8-byte aligned");
+    DeviceRestore restore;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (!query_pointer_ok(h, d_lo) || !query_pointer_ok(h, d_counts) || (list && !query_pointer_ok(h, d_faces)))
+        return fail(h, VRC_ERR_INVALID_ARGUMENT, "extract_faces_device: corners and outputs must be memory the GPU of the handle (device %d) can read and write", h->device);
+    VRC_TRY(wait_for_null_stream(h));
+    FaceCall c;
+    VRC_TRY(faces_count(h, c, static_cast<const int32_t *>(d_lo), n, size, capacity, flags, items, static_cast<int64_t *>(d_counts)));
+    VRC_TRY(faces_emit(h, c, static_cast<int32_t *>(d_faces)));
+    faces_report(info, c.total, capacity, c.seconds);
+    return VRC_OK;
 }
 
 }  // extern "C"

@@ -137,6 +137,9 @@ struct vrc_caster {
     // vrc_get_voxels / vrc_read_regions: staging of the host calls (positions or corners in, values or bytes out)
     int32_t *d_read_in = nullptr; int64_t read_in_capacity = 0;
     void *d_read_out = nullptr; size_t read_out_bytes = 0;
+    // vrc_extract_faces: the faces per (region, brick), their scan and the host call's counts (its corners and its list stage through
+    // d_read_in / d_read_out, the scan's storage is d_box_temp)
+    int64_t *d_face_items = nullptr; int64_t face_item_capacity = 0;
     // the scene edits (vrc_scene_edit.cpp).  d_edit_in: no longer used, every edit stages through d_region_in; the field stays until the
     // scratch gets an owner of its own ("Left out").  Keys and edit numbers (unsorted, sorted), the unique keys
     // and their run lengths; the counters; rocprim's storage; the touched nodes above the bricks (keys) and every touched node's record

@@ -1,6 +1,6 @@
 // Everything the host layer (vrc_api.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
 // vrc_api.cpp and by every file that defines one of these functions, so the compiler holds each definition against its
-// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h, voxel_edit.h, region_write.h and octree_compact.h.
+// declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h, face_extract.h, voxel_edit.h, region_write.h and octree_compact.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +19,7 @@ struct QueryParams;
 struct BoxParams;
 struct SweepParams;
 struct ReadParams;
+struct FaceParams;
 struct EditParams;
 struct EditLevel;
 struct RegionParams;
@@ -71,6 +72,11 @@ hipError_t launch_sweep(const SweepParams &p, hipStream_t stream);
 // voxel_read.hip
 hipError_t launch_voxel_points(const ReadParams &q, hipStream_t stream);
 hipError_t launch_voxel_regions(const ReadParams &q, hipStream_t stream);
+
+// face_extract.hip
+hipError_t launch_face_count(const FaceParams &q, hipStream_t stream);
+hipError_t launch_face_regions(const FaceParams &q, hipStream_t stream);
+hipError_t launch_face_emit(const FaceParams &q, hipStream_t stream);
 
 // voxel_edit.hip
 hipError_t launch_edit_keys(const EditParams &q, hipStream_t stream);
