@@ -1,36 +1,17 @@
 // voxel_edit_emit.hpp -- what every brick pass of an edit ends with, once: voxel_edit.hip (single voxels) and region_write.hip
 // (boxes and dense blocks) differ in how a wave applies its run to the brick and share how the brick becomes a subtree.  Device
-// code only; the Morton helpers compile for the host too.
+// code only; the Morton helpers live in morton3.hpp, which compiles for the host too.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
+#include "morton3.hpp"
 #include "svo_node.hpp"
 #include "voxel_edit.h"
 
 namespace vrc {
-
-// bit k of v to bit 3 k (21 bits), and back
-__host__ __device__ inline uint64_t spread3(uint64_t x) {
-    x &= 0x1fffffULL;
-    x = (x | x << 32) & 0x1f00000000ffffULL;
-    x = (x | x << 16) & 0x1f0000ff0000ffULL;
-    x = (x | x << 8) & 0x100f00f00f00f00fULL;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ULL;
-    x = (x | x << 2) & 0x1249249249249249ULL;
-    return x;
-}
-__host__ __device__ inline uint32_t compact3(uint64_t x) {
-    x &= 0x1249249249249249ULL;
-    x = (x ^ (x >> 2)) & 0x10c30c30c30c30c3ULL;
-    x = (x ^ (x >> 4)) & 0x100f00f00f00f00fULL;
-    x = (x ^ (x >> 8)) & 0x1f0000ff0000ffULL;
-    x = (x ^ (x >> 16)) & 0x1f00000000ffffULL;
-    x = (x ^ (x >> 32)) & 0x1fffffULL;
-    return (uint32_t)x;
-}
 
 // first index in [0, n) whose key is not below `key`
 __device__ inline int64_t lower_bound(const uint64_t *keys, int64_t n, uint64_t key) {
