@@ -672,6 +672,46 @@ int vrc_fill_boxes_device(vrc_caster *h, const void *d_boxes, const void *d_mate
 int vrc_write_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], const int8_t *data, size_t n_bytes, uint32_t flags, vrc_edit_info *info);
 int vrc_write_regions_device(vrc_caster *h, const void *d_lo, int64_t n, const int32_t size[3], const void *d_data, size_t n_bytes, uint32_t flags, vrc_edit_info *info);
 
+/* ---- shape fills ---------------------------------------------------------- */
+
+/* Fill balls and axis-aligned cylinders with a material: an explosion crater, a round tunnel, a well, a pillar.  vrc_fill_boxes
+ * with round operations: an operation is still six integers, and no voxel of it is enumerated on the host or on the device.
+ *
+ * shapes int32[6 n]: kind, cx, cy, cz, r, h.  materials int32[n], each in [-128, 127]; 0 clears.                              */
+#define VRC_SHAPE_BALL        0
+#define VRC_SHAPE_CYLINDER_X  1
+#define VRC_SHAPE_CYLINDER_Y  2
+#define VRC_SHAPE_CYLINDER_Z  3
+/* Membership is defined in integers, so a host can replay it exactly:
+ *   ball                       voxel v is in the shape iff (vx - cx)^2 + (vy - cy)^2 + (vz - cz)^2 <= r^2; r = 0 is the single
+ *                              voxel c; h must be 0.
+ *   cylinder along a = kind-1  voxel v is in the shape iff c_a <= v_a < c_a + h and the squared distance over the other two
+ *                              axes is <= r^2; h >= 1; c_a + h is formed in 64 bits (c_a = INT32_MAX - 1 with h = INT32_MAX is
+ *                              legal).
+ *   0 <= r <= 2^30; c may be any int32.  An axis with |d| > r is outside and is tested first; after that every square is at most
+ *   2^60 and every sum fits signed 64 bits, so nothing wraps and nothing rounds (the one square root, the half width of a row, is
+ *   an exact integer root).
+ * An operation is invalid when its kind is unknown, r is outside [0, 2^30], a ball has h != 0, a cylinder has h < 1 or its
+ * material is outside [-128, 127]: the host call refuses the batch with VRC_ERR_INVALID_ARGUMENT and changes nothing; the _device
+ * call, which cannot look without a read-back, skips that operation and counts it in info->skipped.
+ *
+ * Everything else is vrc_fill_boxes' contract, with "shape" for "box": the operations apply IN INDEX ORDER; flags are
+ * VRC_WRITE_WHERE_EMPTY or VRC_WRITE_WHERE_SOLID, which exclude each other (VRC_WRITE_SKIP_ZERO and any other bit:
+ * VRC_ERR_INVALID_ARGUMENT); the branch follows using_octree; the part of a shape outside the scene is ignored and an operation
+ * with no voxel in the scene is counted in `skipped`; a tree without attachments stays without them while every operation that
+ * has a voxel in the scene has material 0 or 5; the growth bound, edit_reserve, atomicity, the dropped coarse table and boxes, the
+ * group's replication, VRC_ERR_LIMIT for a tree held outside the group, for a map with dy > dz, for n > 2^31 - 1 and for more
+ * than 2^31 - 1 (brick, operation) pairs, the _device variant's pointers and the host rules are the fills'.
+ *
+ * What differs: `bricks_touched`.  A brick is touched iff it holds at least one in-scene voxel of some valid operation -- the
+ * exact set, not the bricks of the bounding box -- and a pair is one such brick of one operation.  That keeps the placement
+ * promise: with flags = 0 the descriptor array, the lookup and the attachments are bit-identical to those vrc_set_voxels
+ * produces for the shapes expanded to their in-scene voxels in operation order.  A batch that changes no voxel appends nothing.
+ * Cost: the front end takes one step per brick row (by, bz) of each shape's bounding box clipped to the scene, the brick pass
+ * one wave per touched brick; nothing scales with r^3.                                                                          */
+int vrc_fill_shapes(vrc_caster *h, const int32_t *shapes, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+int vrc_fill_shapes_device(vrc_caster *h, const void *d_shapes, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info);
+
 /* ---- octree compaction ---------------------------------------------------- */
 
 /* Copy the part of the descriptor array that the root reaches into a new, dense, canonically ordered array on the device, remap

@@ -227,6 +227,8 @@ SIGNATURES = {
     "vrc_fill_boxes_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_write_regions": (C.c_int, [_H, _i32p, C.c_int64, _i32p, C.POINTER(C.c_int8), C.c_size_t, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_write_regions_device": (C.c_int, [_H, C.c_void_p, C.c_int64, _i32p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_fill_shapes": (C.c_int, [_H, _i32p, _i32p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
+    "vrc_fill_shapes_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.POINTER(EditInfo)]),
     "vrc_compact_octree": (C.c_int, [_H, C.c_uint32, C.POINTER(CompactInfo)]),
 }
 LAYOUT_STRICT_REFERENCE, LAYOUT_NO_PAGE_HEADERS, BUILD_COUNT_ONLY = 1, 2, 1
@@ -234,6 +236,8 @@ BUILD_ATTACHMENTS = 2
 COMPACT_DRY_RUN = 1
 # region edits (vrc_fill_boxes / vrc_write_regions): the flags
 WRITE_WHERE_EMPTY, WRITE_WHERE_SOLID, WRITE_SKIP_ZERO = 1, 2, 4
+# shape fills (vrc_fill_shapes): the kinds
+SHAPE_BALL, SHAPE_CYLINDER_X, SHAPE_CYLINDER_Y, SHAPE_CYLINDER_Z = 0, 1, 2, 3
 KERNEL_NONE, KERNEL_SVO, KERNEL_JUMP, KERNEL_ARRAY = 0, 1, 2, 3      # vrc_last_kernel: family
 # ray queries (vrc_cast_rays): the flag, and the bits of record field 5
 RAY_AS_PIXEL = 1
@@ -1088,6 +1092,32 @@ class CLCaster:
             raise VrcError(f"write_regions_device: size must be three integers, got {size}")
         return self._edit_call(lib.vrc_write_regions_device, C.c_void_p(lo_ptr), int(n), _ptr(sz, _i32p), C.c_void_p(data_ptr), int(n_bytes),
                                self._write_flags("write_regions_device", where, skip_zero))
+
+    # -- shape fills (vrc_fill_shapes, include/vrc.h)
+    def fill_shapes(self, shapes: np.ndarray, materials, where: Optional[str] = None) -> dict:
+        """Fill balls and axis-aligned cylinders with materials[i], in index order: shapes (n, 6) int32 = kind (SHAPE_BALL,
+        SHAPE_CYLINDER_X / _Y / _Z), cx, cy, cz, r, h (a ball: h = 0; a cylinder covers [c, c + h) along its axis), materials (n,)
+        or one value; 0 clears, the part outside the scene is ignored.  where as in fill_boxes.  Returns vrc_edit_info as a dict
+        (skipped counts shapes with no voxel in the scene; bricks_touched counts the bricks that hold one).  Raises on failure."""
+        s = np.asarray(shapes)
+        if s.ndim != 2 or s.shape[1] != 6:
+            raise VrcError(f"fill_shapes: shapes must have shape (n, 6), got {s.shape}")
+        m = np.asarray(materials)
+        if m.shape not in ((), (s.shape[0],)):
+            raise VrcError(f"fill_shapes: materials must be one value or have shape ({s.shape[0]},), got {m.shape}")
+        for name, v in (("shape", s), ("material", m)):
+            if v.size and (v.min() < -2 ** 31 or v.max() >= 2 ** 31):
+                raise VrcError(f"fill_shapes: a {name} does not fit int32")
+        s = np.ascontiguousarray(s, dtype=np.int32)
+        m = np.ascontiguousarray(np.broadcast_to(m, (s.shape[0],)), dtype=np.int32)
+        return self._edit_call(lib.vrc_fill_shapes, _ptr(s, _i32p), _ptr(m, _i32p), s.shape[0], self._write_flags("fill_shapes", where))
+
+    def fill_shapes_device(self, shapes_ptr: int, materials_ptr: int, n: int, where: Optional[str] = None) -> dict:
+        """fill_shapes on device memory of this handle's GPU (e.g. torch tensors' data_ptr(): n x 6 int32 and n int32); an
+        invalid shape (unknown kind, r outside [0, 2^30], a ball with h != 0, a cylinder with h < 1) or a material outside
+        [-128, 127] is skipped and counted."""
+        return self._edit_call(lib.vrc_fill_shapes_device, C.c_void_p(shapes_ptr), C.c_void_p(materials_ptr), int(n),
+                               self._write_flags("fill_shapes_device", where))
 
     # -- octree compaction (vrc_compact_octree, include/vrc.h)
     def compact_octree(self, dry_run: bool = False) -> dict:

@@ -203,6 +203,18 @@ public:
         return ok(vrc_set_voxels_device(h_, d_positions, d_materials, n, 0u, info));
     }
 
+    // extension: fill balls and axis-aligned cylinders (vrc_fill_shapes): shapes = 6 int32 each (kind, cx, cy, cz, r, h),
+    // materials = one int32 each in [-128, 127], applied in index order; flags = VRC_WRITE_WHERE_EMPTY / _SOLID or 0
+    bool fill_shapes(const std::vector<int32_t> &shapes, const std::vector<int32_t> &materials, uint32_t flags = 0u, vrc_edit_info *info = nullptr) {
+        if (shapes.size() != 6 * materials.size()) return ok(VRC_ERR_INVALID_ARGUMENT);
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_fill_shapes(h_, shapes.data(), materials.data(), (int64_t)materials.size(), flags, info));
+    }
+    bool fill_shapes_device(const void *d_shapes, const void *d_materials, int64_t n, uint32_t flags = 0u, vrc_edit_info *info = nullptr) {
+        if (info) info->struct_size = (uint32_t)sizeof(*info);
+        return ok(vrc_fill_shapes_device(h_, d_shapes, d_materials, n, flags, info));
+    }
+
     // extension: drop the garbage the edits leave in the resident octree (vrc_compact_octree); dry_run measures only
     bool compact_octree(bool dry_run = false, vrc_compact_info *info = nullptr) {
         if (info) info->struct_size = (uint32_t)sizeof(*info);

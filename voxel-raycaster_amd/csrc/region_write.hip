@@ -12,6 +12,10 @@
 //                                  bytes of its in-scene part
 //   (exclusive scan of the counts: rocprim; the host reads the total)
 //   region_write_emit_kernel       one wave per operation: the pairs (brick key, operation) at offsets[op] + local
+//   shape_write_count_kernel       balls and axis-aligned cylinders (vrc_fill_shapes), one wave per operation: the lanes stride over the
+//   shape_write_emit_kernel        brick rows of the clipped bounding box, and the bricks of a row are a closed form (shape_span.hpp) --
+//                                  the exact set of bricks that hold a voxel of the shape.  The brick pass below takes each row's x range
+//                                  from the same closed form; everything else is the fills'.
 //   (sort by key; the unique keys in order: voxel_edit.hip)
 //   region_write_brick_kernel      tree, one wave per touched brick: lane = row (y, z), its 8 materials in one 64-bit register.
 //                                  The wave walks the run in order -- a wave-uniform loop, the operation's integers are uniform
@@ -26,6 +30,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "region_write.h"
+#include "shape_span.hpp"
 #include "svo_node.hpp"
 #include "voxel_edit_emit.hpp"
 #include "vrc_launch.h"
@@ -39,7 +44,7 @@ namespace {
 __device__ inline bool region_op(const RegionParams &p, int64_t i, int64_t lo[3], int64_t hi[3], int &m) {
     bool ok = true;
     m = 0;
-    if (p.paste) {
+    if (p.mode == kRegionPaste) {
         for (int a = 0; a < 3; a++) { lo[a] = p.boxes[3 * i + a]; hi[a] = lo[a] + p.size[a]; }
     } else {
         for (int a = 0; a < 3; a++) {
@@ -65,6 +70,25 @@ __device__ inline bool region_bricks(const RegionParams &p, const int64_t lo[3],
     return any;
 }
 
+// Shape i as the caller's six integers, and its material
+__device__ inline ShapeOp shape_op(const RegionParams &p, int64_t i, int &m) {
+    const int32_t *s = p.boxes + 6 * i;
+    m = p.materials[i];
+    return ShapeOp{s[0], {s[1], s[2], s[3]}, s[4], s[5]};
+}
+
+// The brick rows (by, bz) of the shape's bounding box, clipped to the scene in 64 bits: b0[1], b0[2] and nb[1], nb[2] (nb[0], b0[0]
+// are not used).  false: the box misses the scene, or the operation is one the _device call could not be refused for.
+__device__ inline bool shape_brick_rows(const RegionParams &p, const ShapeOp &s, int m, int64_t b0[3], int64_t nb[3]) {
+    if (!shape_valid(s, m)) return false;
+    int64_t lo[3], hi[3];
+    for (int a = 0; a < 3; a++) {
+        const ShapeSpan e = shape_extent(s, a);
+        lo[a] = e.a; hi[a] = e.b;
+    }
+    return region_bricks(p, lo, hi, b0, nb);
+}
+
 __device__ inline uint64_t low_bytes(int k) { return k >= 8 ? ~0ULL : (1ULL << (8 * k)) - 1ULL; }
 
 // 0xff in every byte of v that is zero
@@ -81,14 +105,24 @@ __device__ inline uint64_t region_apply_run(const RegionParams &p, int64_t first
         const int64_t op = p.edit.sorted_order[i];
         int64_t lo[3], hi[3];
         int m;
-        (void)region_op(p, op, lo, hi, m);
+        bool yz;                                                    // the row is one of the operation's
+        if (p.mode == kRegionShapes) {
+            // the row's own x range from the closed form (per-lane 64-bit integer work, no branch on it); an empty span: not a row of the shape
+            const ShapeSpan x = shape_row_span(shape_op(p, op, m), gy, gz);
+            lo[0] = x.a; hi[0] = x.b;
+            lo[1] = lo[2] = hi[1] = hi[2] = 0;
+            yz = x.a < x.b;
+        } else {
+            (void)region_op(p, op, lo, hi, m);
+            yz = gy >= lo[1] && gy < hi[1] && gz >= lo[2] && gz < hi[2];
+        }
         const int64_t xe = hi[0] < p.lim[0] ? hi[0] : p.lim[0];
         const int64_t a64 = lo[0] - ox, b64 = xe - ox;
         const int a = a64 < 0 ? 0 : (a64 > 8 ? 8 : (int)a64), b = b64 < 0 ? 0 : (b64 > 8 ? 8 : (int)b64);
-        const bool in = a < b && gy >= lo[1] && gy < hi[1] && gy < p.lim[1] && gz >= lo[2] && gz < hi[2] && gz < p.lim[2];
+        const bool in = a < b && yz && gy < p.lim[1] && gz < p.lim[2];
         uint64_t mask = in ? low_bytes(b) & ~low_bytes(a) : 0ULL;
         uint64_t val = 0x0101010101010101ULL * (uint64_t)(uint8_t)m;
-        if (p.paste) {
+        if (p.mode == kRegionPaste) {
             val = 0;
             if (mask) {
                 // the row's bytes of block `op`, at whatever alignment the block has
@@ -122,7 +156,7 @@ __global__ __launch_bounds__(kEditThreads) void region_write_count_kernel(const 
             if (region_op(p, i, lo, hi, m) && region_bricks(p, lo, hi, b0, nb)) {
                 count = (uint64_t)nb[0] * (uint64_t)nb[1] * (uint64_t)nb[2];      // (at most 2^21 bricks per axis: 63 bits)
                 if (count > (1ULL << 32)) count = 1ULL << 32;                    // (the sum stays below 2^63; the host refuses above 2^31 - 1)
-                if (p.edit.scene.svo && !p.paste && m != 0 && m != 5) atomicOr(&p.edit.counters[kEditMaterials], 1ULL);
+                if (p.edit.scene.svo && p.mode == kRegionFill && m != 0 && m != 5) atomicOr(&p.edit.counters[kEditMaterials], 1ULL);
             } else {
                 atomicAdd(&p.edit.counters[kEditSkipped], 1ULL);
             }
@@ -162,6 +196,76 @@ __global__ __launch_bounds__(kEditThreads) void region_write_emit_kernel(const R
             p.edit.keys[at + l] = p.edit.scene.svo ? spread3(bx) | (spread3(by) << 1) | (spread3(bz) << 2)
                                                    : bx + (uint64_t)p.nb[0] * (by + (uint64_t)p.nb[1] * bz);
             p.edit.order[at + l] = (uint32_t)op;
+        }
+    }
+}
+
+// Shapes, one wave per operation (operation n: the scan's closing zero).  The lanes stride over the brick rows (by, bz) of the
+// shape's clipped bounding box -- so a radius of 2^30 in a 64^3 scene is 8 x 8 rows -- and each row's bricks come from the closed
+// form (shape_span.hpp): the count is the exact number of bricks that hold a voxel of the shape, not the box's.
+__global__ __launch_bounds__(kEditThreads) void shape_write_count_kernel(const RegionParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (kEditThreads / 64);
+    for (int64_t op = (int64_t)blockIdx.x * (kEditThreads / 64) + (threadIdx.x >> 6); op <= p.n; op += waves) {
+        uint64_t count = 0;
+        if (op < p.n) {
+            int m;
+            const ShapeOp s = shape_op(p, op, m);
+            int64_t b0[3], nb[3];
+            if (shape_brick_rows(p, s, m, b0, nb)) {
+                const uint64_t rows = (uint64_t)nb[1] * (uint64_t)nb[2];
+                for (uint64_t l = (uint64_t)lane; l < rows; l += 64) {
+                    const ShapeSpan b = shape_brick_row(s, b0[1] + (int64_t)(l % (uint64_t)nb[1]), b0[2] + (int64_t)(l / (uint64_t)nb[1]), p.lim, kReadBrickLog2);
+                    count += (uint64_t)(b.b - b.a);
+                    if (count > (1ULL << 32)) count = 1ULL << 32;                // (as the boxes': the host refuses above 2^31 - 1)
+                }
+                for (int d = 32; d >= 1; d >>= 1) count += __shfl_down(count, d, 64);
+                count = __shfl(count, 0, 64);
+                if (count > (1ULL << 32)) count = 1ULL << 32;
+            }
+            if (lane == 0) {
+                if (!count) atomicAdd(&p.edit.counters[kEditSkipped], 1ULL);
+                else if (p.edit.scene.svo && m != 0 && m != 5) atomicOr(&p.edit.counters[kEditMaterials], 1ULL);
+            }
+        }
+        if (lane == 0) p.counts[op] = count;
+    }
+}
+
+// The same stride; every round takes a wave-wide exclusive prefix of the lanes' interval lengths on top of a running base, and a
+// lane writes its row's bricks there.  The order of the pairs inside one operation is free: the stable sort needs the operations
+// ascending, and offsets[] gives that.
+__global__ __launch_bounds__(kEditThreads) void shape_write_emit_kernel(const RegionParams p) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (kEditThreads / 64);
+    for (int64_t op = (int64_t)blockIdx.x * (kEditThreads / 64) + (threadIdx.x >> 6); op < p.n; op += waves) {
+        const uint64_t count = p.counts[op], at = p.offsets[op];
+        if (!count) continue;
+        int m;
+        const ShapeOp s = shape_op(p, op, m);
+        int64_t b0[3], nb[3];
+        (void)shape_brick_rows(p, s, m, b0, nb);
+        const uint64_t rows = (uint64_t)nb[1] * (uint64_t)nb[2];
+        uint64_t base = 0;
+        for (uint64_t first = 0; first < rows; first += 64) {      // (every lane takes every round: the prefix is the wave's)
+            const uint64_t l = first + (uint64_t)lane;
+            const uint64_t by = (uint64_t)b0[1] + l % (uint64_t)nb[1], bz = (uint64_t)b0[2] + l / (uint64_t)nb[1];
+            ShapeSpan b = {0, 0};
+            if (l < rows) b = shape_brick_row(s, (int64_t)by, (int64_t)bz, p.lim, kReadBrickLog2);
+            const uint64_t len = (uint64_t)(b.b - b.a);
+            uint64_t upto = len;                                    // inclusive prefix
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint64_t below = __shfl_up(upto, d, 64);
+                if (lane >= d) upto += below;
+            }
+            const uint64_t local = base + upto - len;
+            for (uint64_t j = 0; j < len && local + j < count; j++) {            // (never past the operation's own pairs)
+                const uint64_t bx = (uint64_t)b.a + j;
+                p.edit.keys[at + local + j] = p.edit.scene.svo ? spread3(bx) | (spread3(by) << 1) | (spread3(bz) << 2)
+                                                               : bx + (uint64_t)p.nb[0] * (by + (uint64_t)p.nb[1] * bz);
+                p.edit.order[at + local + j] = (uint32_t)op;
+            }
+            base += __shfl(upto, 63, 64);
         }
     }
 }
@@ -236,6 +340,18 @@ hipError_t region_scan(void *temp, size_t *temp_bytes, const uint64_t *in, uint6
 hipError_t launch_region_emit(const RegionParams &p, hipStream_t stream) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(region_write_emit_kernel, dim3(region_grid_for(p.n * 64)), dim3(kEditThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_shape_count(const RegionParams &p, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(shape_write_count_kernel, dim3(region_grid_for((p.n + 1) * 64)), dim3(kEditThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_shape_emit(const RegionParams &p, hipStream_t stream) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(shape_write_emit_kernel, dim3(region_grid_for(p.n * 64)), dim3(kEditThreads), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -93,6 +93,8 @@ hipError_t launch_region_count(const RegionParams &p, hipStream_t stream);
 hipError_t launch_region_materials(const RegionParams &p, hipStream_t stream);
 hipError_t region_scan(void *temp, size_t *temp_bytes, const uint64_t *in, uint64_t *out, int64_t n, hipStream_t stream);
 hipError_t launch_region_emit(const RegionParams &p, hipStream_t stream);
+hipError_t launch_shape_count(const RegionParams &p, hipStream_t stream);
+hipError_t launch_shape_emit(const RegionParams &p, hipStream_t stream);
 hipError_t launch_region_bricks(const RegionParams &p, hipStream_t stream);
 
 // octree_compact.hip

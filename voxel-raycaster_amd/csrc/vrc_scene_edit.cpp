@@ -1,5 +1,5 @@
 // vrc_scene_edit.cpp -- the calls of include/vrc.h that change the resident scene: point edits (vrc_set_voxels, voxel_edit.hip),
-// region edits (vrc_fill_boxes / vrc_write_regions, region_write.hip) and the compaction of the octree (vrc_compact_octree,
+// region edits (vrc_fill_boxes / vrc_write_regions / vrc_fill_shapes, region_write.hip) and the compaction of the octree (vrc_compact_octree,
 // octree_compact.hip), with their _device variants.
 //
 // They are one procedure.  On every rank of the group (run_group) a STAGE takes the tree's guard, drains the stream and binds the
@@ -8,6 +8,7 @@
 // tree is what it was.  Then every rank commits (edit_commit), every rank's root moves, and the call's info struct is written.
 #include "octree_compact.h"
 #include "region_write.h"
+#include "shape_span.hpp"
 #include "voxel_edit.h"
 #include "vrc_host.hpp"
 
@@ -191,13 +192,13 @@ int run_group(vrc_caster *h, bool svo, std::vector<std::unique_ptr<Stage>> &stag
 }
 
 // What a call hands to every rank: its name, its two arrays -- positions (int32[3 n]) and materials (int32[n]); boxes (int32[6 n])
-// and materials; corners (int32[3 n]) and blocks (n * volume bytes) -- in host memory or in memory rank 0's GPU can read, and for
+// and materials; corners (int32[3 n]) and blocks (n * volume bytes); shapes (int32[6 n]) and materials -- in host memory or in memory rank 0's GPU can read, and for
 // the region edits what they do with them.
-enum EditKind { kPoints = 0, kFill, kPaste };
+enum EditKind { kPoints = 0, kFill, kPaste, kShapes };
 struct EditBatch {
     const char *what; const void *first, *second; int64_t n; bool on_device;
     EditKind kind; uint32_t flags; int32_t size[3] = {0, 0, 0}; uint64_t volume = 0;
-    size_t first_bytes() const { return sizeof(int32_t) * (kind == kFill ? 6 : 3) * (size_t)n; }
+    size_t first_bytes() const { return sizeof(int32_t) * (kind == kFill || kind == kShapes ? 6 : 3) * (size_t)n; }
     size_t second_bytes() const { return kind == kPaste ? (size_t)volume * (size_t)n : sizeof(int32_t) * (size_t)n; }
 };
 
@@ -342,7 +343,8 @@ int region_stage(vrc_caster *g, const EditBatch &b, const int32_t *d_first, cons
     const bool svo = q.scene.svo != 0;
     const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);
     const bool paste = b.kind == kPaste;
-    rp.boxes = d_first; rp.n = n; rp.paste = paste; rp.flags = b.flags; rp.volume = b.volume;
+    const bool shapes = b.kind == kShapes;
+    rp.boxes = d_first; rp.n = n; rp.mode = paste ? vrc::kRegionPaste : shapes ? vrc::kRegionShapes : vrc::kRegionFill; rp.flags = b.flags; rp.volume = b.volume;
     if (paste) rp.data = static_cast<const int8_t *>(d_second); else rp.materials = static_cast<const int32_t *>(d_second);
     for (int a = 0; a < 3; a++) { rp.size[a] = b.size[a]; rp.lim[a] = q.scene.map_dim[a]; }
     // the map's rows at z >= dy have an index past the array (dy <= dz: edit_call): they are outside the scene
@@ -367,7 +369,7 @@ int region_stage(vrc_caster *g, const EditBatch &b, const int32_t *d_first, cons
     // the bricks every operation overlaps, their scan, and the one read-back the sizes of everything else depend on
     HIP_TRY(g, hipMemsetAsync(q.counters, 0, sizeof(c), g->stream));
     HIP_TRY(g, timer.start());
-    HIP_TRY(g, vrc::launch_region_count(rp, g->stream));
+    HIP_TRY(g, shapes ? vrc::launch_shape_count(rp, g->stream) : vrc::launch_region_count(rp, g->stream));
     if (rp.scan_materials) HIP_TRY(g, vrc::launch_region_materials(rp, g->stream));
     HIP_TRY(g, vrc::region_scan(g->d_edit_temp, &scan_bytes, rp.counts, rp.offsets, n + 1, g->stream));
     HIP_TRY(g, timer.stop());
@@ -379,7 +381,7 @@ int region_stage(vrc_caster *g, const EditBatch &b, const int32_t *d_first, cons
     if (pairs > (uint64_t)INT32_MAX) return fail(g, VRC_ERR_LIMIT, "%s: more than 2^31 - 1 (brick, operation) pairs", b.what);
 
     // the pairs, sorted by brick (stable: a brick's operations stay in index order), and the touched bricks in key order
-    VRC_TRY(sort_keys(g, q, (int64_t)pairs, bits, true, timer, [&]() { return vrc::launch_region_emit(rp, g->stream); }));
+    VRC_TRY(sort_keys(g, q, (int64_t)pairs, bits, true, timer, [&]() { return shapes ? vrc::launch_shape_emit(rp, g->stream) : vrc::launch_region_emit(rp, g->stream); }));
     HIP_TRY(g, timer.end(c + vrc::kEditRuns, q.counters + vrc::kEditRuns, sizeof(c[0])));
     const int64_t nb = (int64_t)c[vrc::kEditRuns];
     if (nb <= 0) return VRC_OK;
@@ -441,11 +443,12 @@ int write_device_pointers(vrc_caster *h, const void *d_first, const void *d_seco
     return VRC_OK;
 }
 
-// what the three kinds of call differ in before they run: their flag bits and their words for the arrays and for what a batch holds
+// what the four kinds of call differ in before they run: their flag bits and their words for the arrays and for what a batch holds
 const struct { uint32_t known; const char *arrays, *items, *aligned, *readable; } kEditKinds[] = {
     {0, "positions or materials", "edits", "positions and materials", "positions and materials"},
     {VRC_WRITE_WHERE_EMPTY | VRC_WRITE_WHERE_SOLID, "boxes or materials", "operations", "boxes and materials", "the arrays"},
     {VRC_WRITE_WHERE_EMPTY | VRC_WRITE_WHERE_SOLID | VRC_WRITE_SKIP_ZERO, "corners or data", "operations", "the corners", "the arrays"},
+    {VRC_WRITE_WHERE_EMPTY | VRC_WRITE_WHERE_SOLID, "shapes or materials", "operations", "shapes and materials", "the arrays"},
 };
 
 // One call: the argument checks, then the readiness checks of the ray queries and what the branch needs on top, then what only a
@@ -483,6 +486,12 @@ int edit_call(vrc_caster *h, EditBatch b, const int32_t *size, size_t n_bytes, v
         for (int a = 0; a < 3 && b.kind == kFill; a++)
             if (boxes[6 * i + 3 + a] < 1)
                 return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: box %lld has size[%d] = %d < 1", what, (long long)i, a, (int)boxes[6 * i + 3 + a]);
+        if (b.kind == kShapes) {
+            const int32_t *s = boxes + 6 * i;
+            if (!vrc::shape_valid(vrc::ShapeOp{s[0], {s[1], s[2], s[3]}, s[4], s[5]}, materials[i]))
+                return fail(h, VRC_ERR_INVALID_ARGUMENT, "%s: shape %lld has kind = %d, r = %d, h = %d: the kind is 0 .. 3, r is in [0, 2^30], a ball has h = 0 and a cylinder h >= 1",
+                            what, (long long)i, (int)s[0], (int)s[4], (int)s[5]);
+        }
     }
     return edit_run(h, b, info);
 }
@@ -685,6 +694,12 @@ int vrc_fill_boxes(vrc_caster *h, const int32_t *boxes, const int32_t *materials
 }
 int vrc_fill_boxes_device(vrc_caster *h, const void *d_boxes, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
     return edit_call(h, {"fill_boxes_device", d_boxes, d_materials, n, true, kFill, flags}, nullptr, 0, info);
+}
+int vrc_fill_shapes(vrc_caster *h, const int32_t *shapes, const int32_t *materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
+    return edit_call(h, {"fill_shapes", shapes, materials, n, false, kShapes, flags}, nullptr, 0, info);
+}
+int vrc_fill_shapes_device(vrc_caster *h, const void *d_shapes, const void *d_materials, int64_t n, uint32_t flags, vrc_edit_info *info) {
+    return edit_call(h, {"fill_shapes_device", d_shapes, d_materials, n, true, kShapes, flags}, nullptr, 0, info);
 }
 int vrc_write_regions(vrc_caster *h, const int32_t *lo, int64_t n, const int32_t size[3], const int8_t *data, size_t n_bytes, uint32_t flags, vrc_edit_info *info) {
     return edit_call(h, {"write_regions", lo, data, n, false, kPaste, flags}, size, n_bytes, info);
