@@ -129,7 +129,7 @@ def test_every_voxel_of_every_box_is_empty_on_the_host(make, atlas):
     machinery: an independent walk of the descriptor array gives every empty child slot its cube, the word gives the box, and
     the dense grid the tree was generated from must hold no solid voxel anywhere inside it.  Also: every box contains its own
     node (extents are non-negative by construction) and boxes do grow (the structure is not vacuous)."""
-    import treetools
+    import box_check
     s = make()
     dim = s["dim"]
     grid = np.asarray(s["grid"]).reshape(dim, dim, dim) != 0          # [z, y, x]
@@ -140,25 +140,8 @@ def test_every_voxel_of_every_box_is_empty_on_the_host(make, atlas):
     words = c.read_empty_boxes()
     assert words.shape == (o.descriptor_buffer.size, 8)
     # solid voxels in any box in O(1): a summed-volume table of the dense grid, S[z, y, x] = solids in [0, z) x [0, y) x [0, x)
-    S = np.zeros((dim + 1, dim + 1, dim + 1), dtype=np.int64)
-    S[1:, 1:, 1:] = grid.astype(np.int64).cumsum(0).cumsum(1).cumsum(2)
-
-    def solids(x0, y0, z0, x1, y1, z1):
-        return int(S[z1, y1, x1] - S[z0, y1, x1] - S[z1, y0, x1] - S[z1, y1, x0] + S[z0, y0, x1] + S[z0, y1, x0] + S[z1, y0, x0] - S[z0, y0, x0])
-
-    assert solids(0, 0, 0, dim, dim, dim) == int(grid.sum()) > 0
-    n_boxes = grown = 0
-    volume = node_volume = 0
-    for index, k, (x, y, z), size in treetools.empty_children(o.descriptor_buffer, o.root_index, dim):
-        w = int(words[index, k])
-        ext = [treetools.box_decode((w >> (5 * j)) & 31) * size for j in range(6)]      # -x -y -z +x +y +z
-        x0, y0, z0 = max(x - ext[0], 0), max(y - ext[1], 0), max(z - ext[2], 0)
-        x1, y1, z1 = min(x + size + ext[3], dim), min(y + size + ext[4], dim), min(z + size + ext[5], dim)
-        assert solids(x0, y0, z0, x1, y1, z1) == 0, f"descriptor {index} slot {k}: the box {(x0, y0, z0)}..{(x1, y1, z1)} of the {size}^3 node at {(x, y, z)} holds a solid voxel"
-        n_boxes += 1
-        grown += any(ext)
-        volume += (x1 - x0) * (y1 - y0) * (z1 - z0)
-        node_volume += size ** 3
+    assert int(box_check.solids(box_check.summed_volume(grid), 0, 0, 0, dim, dim, dim)) == int(grid.sum()) > 0
+    n_boxes, grown, volume, node_volume = box_check.check_boxes(o.descriptor_buffer, o.root_index, dim, words, grid)
     assert n_boxes > 20 and grown > n_boxes // 4
     print(f"\n{s['name']}: {n_boxes} empty child slots, {grown} of them widened; mean box volume {volume / n_boxes:.0f} voxels "
           f"({volume / node_volume:.1f} x the nodes')")

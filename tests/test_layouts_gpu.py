@@ -17,6 +17,7 @@ import gc
 import numpy as np
 import pytest
 
+import box_check
 import box_replay as br
 import ray_replay
 import relayout as rl
@@ -213,21 +214,8 @@ def test_empty_boxes(case):
     words = c.read_empty_boxes()
     assert words.shape == (desc.size, 8)
     solid = case.g.reshape(dim, dim, dim) != 0                  # [z, y, x]
-    S = np.zeros((dim + 1,) * 3, dtype=np.int64)
-    S[1:, 1:, 1:] = solid.astype(np.int64).cumsum(0).cumsum(1).cumsum(2)
-
-    def solids(x0, y0, z0, x1, y1, z1):
-        return int(S[z1, y1, x1] - S[z0, y1, x1] - S[z1, y0, x1] - S[z1, y1, x0] + S[z0, y0, x1] + S[z0, y1, x0] + S[z1, y0, x0] - S[z0, y0, x0])
-
-    grown = 0
-    for index, k, (x, y, z), size in slots:
-        w = int(words[index, k])
-        ext = [treetools.box_decode((w >> (5 * j)) & 31) * size for j in range(6)]      # -x -y -z +x +y +z
-        x0, y0, z0 = max(x - ext[0], 0), max(y - ext[1], 0), max(z - ext[2], 0)
-        x1, y1, z1 = min(x + size + ext[3], dim), min(y + size + ext[4], dim), min(z + size + ext[5], dim)
-        assert solids(x0, y0, z0, x1, y1, z1) == 0, f"{case.tag}: descriptor {index} slot {k}: the box {(x0, y0, z0)}..{(x1, y1, z1)} holds a solid voxel"
-        grown += any(ext)
-    assert grown > len(slots) // 4
+    n_boxes, grown, _, _ = box_check.check_boxes(desc, root, dim, words, solid, tag=case.tag)
+    assert n_boxes == len(slots) and grown > len(slots) // 4
 
 
 @functools.lru_cache(maxsize=None)
