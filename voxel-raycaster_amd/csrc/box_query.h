@@ -1,5 +1,5 @@
 // Kernel-argument block of the batched box-overlap queries (vrc_box_intersection / vrc_box_intersection_device,
-// include/vrc.h), shared by the host layer (vrc_api.cpp) and box_query.hip.  The scene is a SceneView (vrc_params.h), as in
+// include/vrc.h), shared by the host layer (vrc_query.cpp) and box_query.hip.  The scene is a SceneView (vrc_params.h), as in
 // QueryParams (raycast_query.h); the scratch pointers are the host layer's, sized from what the plan pass reports.  Nothing
 // of a frame's buffers is in here.
 #pragma once

@@ -1,5 +1,5 @@
 // Kernel-argument block of the batched swept-box queries (vrc_sweep_boxes / vrc_sweep_boxes_device, include/vrc.h), shared by
-// the host layer (vrc_api.cpp) and box_sweep.hip.  The scene, the sweeps and the start test's results are a BoxParams: the
+// the host layer (vrc_query.cpp) and box_sweep.hip.  The scene, the sweeps and the start test's results are a BoxParams: the
 // start boxes go through the box query's own passes (box_query.hip, box_stride 9, a list of one voxel) before the sweep kernels run.
 #pragma once
 

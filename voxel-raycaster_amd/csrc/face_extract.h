@@ -1,5 +1,5 @@
 // Kernel-argument block of the face extraction (vrc_extract_faces / vrc_extract_faces_device, include/vrc.h), shared by the host
-// layer (vrc_api.cpp) and face_extract.hip.  The scene is a SceneView (vrc_params.h), as in ReadParams (voxel_read.h); the
+// layer (vrc_query.cpp) and face_extract.hip.  The scene is a SceneView (vrc_params.h), as in ReadParams (voxel_read.h); the
 // regions, their bricks and the numbering of the waves are the region read's.
 #pragma once
 

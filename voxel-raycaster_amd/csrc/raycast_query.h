@@ -1,5 +1,5 @@
 // Kernel-argument block of the batched ray queries (vrc_cast_rays / vrc_cast_rays_device, include/vrc.h), shared by the
-// host layer (vrc_api.cpp) and raycast_query.hip.  The scene is a SceneView (vrc_params.h), bound by the host layer's
+// host layer (vrc_query.cpp) and raycast_query.hip.  The scene is a SceneView (vrc_params.h), bound by the host layer's
 // bind_scene like every query family's; nothing of a frame's buffers (image, hit records, counters, the frame constants) is
 // in here, so a query cannot disturb what a frame reports.
 #pragma once

@@ -1,5 +1,5 @@
 // Kernel-argument block of the voxel reads (vrc_get_voxels / vrc_read_regions and their _device variants, include/vrc.h),
-// shared by the host layer (vrc_api.cpp) and voxel_read.hip.  The scene is a SceneView (vrc_params.h), as in BoxParams
+// shared by the host layer (vrc_query.cpp) and voxel_read.hip.  The scene is a SceneView (vrc_params.h), as in BoxParams
 // (box_query.h).  There is no scratch: a read is one launch.
 #pragma once
 

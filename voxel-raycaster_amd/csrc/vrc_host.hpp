@@ -1,7 +1,7 @@
-// vrc_host.hpp -- what the files of the host layer share (vrc_api.cpp: handles, settings, trees, groups, frames and queries;
-// vrc_scene_edit.cpp: the calls that change the resident scene).  Internal: not installed, not part of include/vrc.h.  The
-// helpers are defined in vrc_api.cpp unless a comment says otherwise; they live in namespace vrc_host so that nothing collides
-// with the C names.
+// vrc_host.hpp -- what the files of the host layer share (vrc_api.cpp: handles, settings, trees, groups and frames; vrc_query.cpp:
+// the calls that read the resident scene; vrc_scene_edit.cpp: the calls that change it).  Internal: not installed, not part of
+// include/vrc.h.  The helpers are defined in vrc_api.cpp, those from bind_scene to volume_check in vrc_query.cpp; they live in
+// namespace vrc_host so that nothing collides with the C names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -213,6 +213,8 @@ int set_setting(vrc_caster *h, const char *name, const char *define, int64_t val
 int log2_exact(int64_t v);
 // the tree's empty boxes, in either form
 void release_boxes(vrc_tree *t);
+// materials are bound as a pair or not at all (the frame's RaycastParams and the queries' SceneView); the caller holds t->guard
+void bind_attachments(const vrc_tree *t, const uint32_t *&attach_lookup, const uint64_t *&attachments);
 // The scene a query runs against (the SceneView of QueryParams, BoxParams and ReadParams), from the handle's settings and its
 // tree.  The caller holds t->guard.
 void bind_scene(const vrc_caster *h, const vrc_tree *t, vrc::SceneView &q);
@@ -254,6 +256,29 @@ void write_info(Info *info, Info &out) {
     out.struct_size = bytes;
     memcpy(info, &out, bytes);
 }
+
+// The kernels of a call run in segments on the handle's stream; the device time of each, between two events, is added to *seconds.
+struct SegmentTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t stream = nullptr; double *seconds = nullptr;
+    ~SegmentTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipError_t init(hipStream_t s, double *sum) { stream = s; seconds = sum; hipError_t e = hipEventCreate(&a); return e == hipSuccess ? hipEventCreate(&b) : e; }
+    hipError_t start() { return hipEventRecord(a, stream); }
+    // the segment's last kernel is in the stream: what the caller enqueues between here and wait() (a read-back) is not timed
+    hipError_t stop() { return hipEventRecord(b, stream); }
+    hipError_t wait() {
+        float ms = 0.f;
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (e == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) *seconds += ms * 1e-3; else (void)hipGetLastError();
+        return e;
+    }
+    // stop, the read-back that sizes the next segment (if any), wait
+    hipError_t end(void *host = nullptr, const void *dev = nullptr, size_t bytes = 0) {
+        hipError_t e = stop();
+        if (e == hipSuccess && host) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream);
+        return e == hipSuccess ? wait() : e;
+    }
+};
 
 #ifdef VRC_INDEX_AUDIT
 // The index-audit build (index_audit.hpp): the extents of the arrays the kernels index, published to the device table of every .hip

@@ -1,5 +1,5 @@
-// Everything the host layer (vrc_api.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
-// vrc_api.cpp and by every file that defines one of these functions, so the compiler holds each definition against its
+// Everything the host layer (vrc_api.cpp, vrc_query.cpp, vrc_scene_edit.cpp) calls in the .hip files: the kernel launchers and the device builders.  Included by
+// them and by every file that defines one of these functions, so the compiler holds each definition against its
 // declaration.  The argument blocks themselves live in vrc_params.h, raycast_query.h, box_query.h, box_sweep.h, voxel_read.h, face_extract.h, voxel_edit.h, region_write.h and octree_compact.h.
 #pragma once
 

@@ -101,7 +101,7 @@ inline uint64_t coarse_index(unsigned cx, unsigned cy, unsigned cz, int lc) {
 constexpr int coarse_level_for_depth(int n) { return n >= 14 ? kCoarseMaxLog2 + 1 : n >= 5 ? (n - 2 < kCoarseMaxLog2 ? n - 2 : kCoarseMaxLog2) : 0; }
 
 // The resident scene as the query kernels see it (QueryParams, BoxParams, ReadParams embed one; RaycastParams, the frame
-// kernels' block, keeps its own fields).  The host layer fills it in one place (bind_scene / bind_attachments, vrc_api.cpp).
+// kernels' block, keeps its own fields).  The host layer fills it in one place (bind_scene, vrc_query.cpp; bind_attachments, vrc_api.cpp).
 struct SceneView {
     int32_t svo;                      // using_octree == 0: the tree; else the dense char map
     const int8_t *map;                // array branch

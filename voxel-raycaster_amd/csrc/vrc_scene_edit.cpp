@@ -4,7 +4,7 @@
 //
 // They are one procedure.  On every rank of the group (run_group) a STAGE takes the tree's guard, drains the stream and binds the
 // scene without its coarse table (stage_begin), runs its kernels in timed segments, each ended by the read-back that sizes the
-// next one (EditTimer), and leaves new arrays beside the tree's where the old ones have no room (stage_array).  Until then the
+// next one (SegmentTimer), and leaves new arrays beside the tree's where the old ones have no room (stage_array).  Until then the
 // tree is what it was.  Then every rank commits (edit_commit), every rank's root moves, and the call's info struct is written.
 #include "octree_compact.h"
 #include "region_write.h"
@@ -55,33 +55,10 @@ struct EditStage {
     }
 };
 
-// The kernels of a stage run in segments on the handle's stream; the device time of each, between two events, is added to *seconds.
-struct EditTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t stream = nullptr; double *seconds = nullptr;
-    ~EditTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    hipError_t init(hipStream_t s, double *sum) { stream = s; seconds = sum; hipError_t e = hipEventCreate(&a); return e == hipSuccess ? hipEventCreate(&b) : e; }
-    hipError_t start() { return hipEventRecord(a, stream); }
-    // the segment's last kernel is in the stream: what the caller enqueues between here and wait() (a read-back) is not timed
-    hipError_t stop() { return hipEventRecord(b, stream); }
-    hipError_t wait() {
-        float ms = 0.f;
-        const hipError_t e = hipStreamSynchronize(stream);
-        if (e == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) *seconds += ms * 1e-3; else (void)hipGetLastError();
-        return e;
-    }
-    // stop, the read-back that sizes the next segment (if any), wait
-    hipError_t end(void *host = nullptr, const void *dev = nullptr, size_t bytes = 0) {
-        hipError_t e = stop();
-        if (e == hipSuccess && host) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream);
-        return e == hipSuccess ? wait() : e;
-    }
-};
-
 // What every stage opens with (current device: g->device): the tree's guard, which stays with the caller's lock; a frame in
 // flight finishes first; the scene without its table (the table goes with the edit: every descent starts at the root); the timer.
 // counters: where the edits want their counters, allocated on first use.
-int stage_begin(vrc_caster *g, EditStage &st, std::unique_lock<std::mutex> &lock, EditTimer &timer, vrc::SceneView &scene,
+int stage_begin(vrc_caster *g, EditStage &st, std::unique_lock<std::mutex> &lock, SegmentTimer &timer, vrc::SceneView &scene,
                 unsigned long long **counters = nullptr) {
     st.h = g; st.ran = true;
     lock = std::unique_lock<std::mutex>(g->tree->guard);
@@ -98,7 +75,7 @@ int stage_begin(vrc_caster *g, EditStage &st, std::unique_lock<std::mutex> &lock
 // unique keys and their run lengths.  Opens a timed segment with write_keys, the kernel that fills q.keys / q.order, and leaves
 // the segment open: the caller adds to it and ends it.
 template <class Launch>
-int sort_keys(vrc_caster *g, vrc::EditParams &q, int64_t n, int bits, bool runs, EditTimer &timer, Launch write_keys) {
+int sort_keys(vrc_caster *g, vrc::EditParams &q, int64_t n, int bits, bool runs, SegmentTimer &timer, Launch write_keys) {
     VRC_TRY(grow(g, g->edit_capacity, n, {{g->d_edit_keys, sizeof(uint64_t) * 2 * (size_t)n}, {g->d_edit_order, sizeof(uint32_t) * 2 * (size_t)n},
                                     {g->d_edit_unique, sizeof(uint64_t) * (size_t)n}, {g->d_edit_counts, sizeof(uint32_t) * (size_t)n}}));
     q.n = n;
@@ -206,7 +183,7 @@ struct EditBatch {
 // d_unique the keys of the nb touched bricks in order, c the counters as read so far): size the appended range, make room,
 // run the brick pass -- the region edits' own when `region` is given, which then takes q as its edit block -- and the ancestor
 // pass of every level, and fill the stage for the commit.
-int edit_append(vrc_caster *g, vrc::EditParams &q, vrc::RegionParams *region, int64_t nb, unsigned long long *c, EditTimer &timer, EditStage &st,
+int edit_append(vrc_caster *g, vrc::EditParams &q, vrc::RegionParams *region, int64_t nb, unsigned long long *c, SegmentTimer &timer, EditStage &st,
                 const char *what) {
     vrc_tree *t = g->tree.get();
     const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);   // levels above the bricks
@@ -305,7 +282,7 @@ int edit_stage(vrc_caster *g, const int32_t *d_pos, const int32_t *d_mat, int64_
     vrc::EditParams q;
     memset(&q, 0, sizeof(q));
     std::unique_lock<std::mutex> lock;
-    EditTimer timer;
+    SegmentTimer timer;
     VRC_TRY(stage_begin(g, st, lock, timer, q.scene, &q.counters));
     const bool svo = q.scene.svo != 0;
     const int nlog = q.scene.log2_dim, above = std::max(nlog - vrc::kReadBrickLog2, 0);   // levels above the bricks
@@ -337,7 +314,7 @@ int region_stage(vrc_caster *g, const EditBatch &b, const int32_t *d_first, cons
     memset(&rp, 0, sizeof(rp));
     vrc::EditParams &q = rp.edit;
     std::unique_lock<std::mutex> lock;
-    EditTimer timer;
+    SegmentTimer timer;
     VRC_TRY(stage_begin(g, st, lock, timer, q.scene, &q.counters));
     const int64_t n = b.n;
     const bool svo = q.scene.svo != 0;
@@ -533,7 +510,7 @@ int compact_stage(vrc_caster *g, bool dry, CompactStage &st) {
     vrc::CompactParams q;
     memset(&q, 0, sizeof(q));
     std::unique_lock<std::mutex> lock;
-    EditTimer timer;                  // (the kernels run in segments, each ended by the read-back that sizes the next one)
+    SegmentTimer timer;                  // (the kernels run in segments, each ended by the read-back that sizes the next one)
     VRC_TRY(stage_begin(g, st, lock, timer, q.scene));
     vrc_tree *t = g->tree.get();
     const int n = q.scene.log2_dim;
